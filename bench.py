@@ -408,6 +408,77 @@ def run_alt_pass(args, rank, world, dev, native=False):
     return res
 
 
+DUMP_BYTES = 64 * 2 ** 20    # --dump-outputs: hard limit of what one run writes
+DUMP_SAMPLE_BYTES = 32 * 2 ** 20   # ... and what the samples of the large tensors are sized for
+
+
+def training_state(opt, dev):
+    """what a training step reads besides the batch: the optimizer arenas (bf16 parameters, fp32 master, moments), the step
+    count, and the host / device random streams (masks, mixing plans, dropout seeds, instance sampling)"""
+    from unispeech_amd import functional as WF
+    return {"arenas": [t.clone() for t in (opt.flat_param, opt.master, opt.exp_avg, opt.exp_avg_sq)], "step": opt.step_count,
+            "np": np.random.get_state(), "torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(dev),
+            "seed_ctr": WF._SEED_CTR[0]}
+
+
+def restore_training_state(opt, dev, st):
+    from unispeech_amd import functional as WF
+    for dst, src in zip((opt.flat_param, opt.master, opt.exp_avg, opt.exp_avg_sq), st["arenas"]):
+        dst.copy_(src)
+    opt.step_count = st["step"]
+    opt._params_written()
+    np.random.set_state(st["np"])
+    torch.set_rng_state(st["torch"])
+    torch.cuda.set_rng_state(st["cuda"], dev)
+    WF._SEED_CTR[0] = st["seed_ctr"]
+
+
+def _sample_index(name, numel, k):
+    """k sorted flat indices of a tensor of numel elements, seeded by its name only (identical from run to run and build to build)"""
+    if k >= numel:
+        return None
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.sort(rng.choice(numel, size=k, replace=False))
+
+
+def _sampled(name, t, k):
+    flat = t.detach().reshape(-1)
+    idx = _sample_index(name, flat.numel(), k)
+    if idx is not None:
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def step_outputs(result, sample_size, model, extract):
+    """{name: float32 / float64 array} of what the last step handed its caller: the features of an extract call, or the loss,
+    the sample size and every parameter's gradient and updated value of a training step.  Larger tensors are represented by a
+    fixed sample of their elements (_sample_index) sized to DUMP_SAMPLE_BYTES in all."""
+    if extract:
+        return {"features": _sampled("features", result, DUMP_SAMPLE_BYTES // 4)}
+    out = {"loss": np.asarray(float(result.item()), dtype=np.float64),
+           "sample_size": np.asarray(float(sample_size), dtype=np.float64)}
+    named = [(n, p) for n, p in model.named_parameters() if p.grad is not None]
+    # per-tensor cap: the largest power of two whose gradient + parameter samples fit the budget
+    cap = 2 ** 24
+    while cap > 1 and 2 * 4 * sum(min(p.numel(), cap) for _, p in named) > DUMP_SAMPLE_BYTES:
+        cap //= 2
+    for n, p in named:
+        out["grad." + n] = _sampled(n, p.grad, cap)
+        out["param." + n] = _sampled(n, p, cap)
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= DUMP_BYTES, total
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -443,10 +514,18 @@ def main():
                     help="1 GPU: run the step through the data-parallel machinery of a rank (DataParallelWavLM over a one-rank gloo "
                          "group: bucketed reducer on its side stream, gradient listeners, reserved CUs, the sample-size all-reduce) -- "
                          "what the N > 1 path costs a rank before any byte crosses a link; the line carries a `data_parallel` block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all): training configs the loss, the sample size and, per parameter, a fixed seeded "
+                         "sample of its gradient and of its updated value; extract a fixed seeded sample of the features.  The "
+                         "timed steps then start from the state after the warm-up (the settling steps are undone), so that two "
+                         "runs with the same arguments compute from identical inputs")
     ap.add_argument("--reserved-cus", type=int, default=-1,
                     help="1 GPU: shrink the persistent GEMM grids by this many CUs as the data-parallel reducer does "
                          "(WAVLM_DP_RESERVED_CUS) -- what the reservation alone costs a rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rendezvous on 127.0.0.1),
@@ -550,6 +629,7 @@ def main():
             sample["net_input"]["source"] = ops.mix_utterances(raw, WF.h2d(ops_np.reshape(-1), dev), ops_np.shape[0],
                                                                 WF.h2d(begin_np, dev), None, True, torch.bfloat16)
         loss, ss, _ = crit(net, sample)
+        last_ss[0] = ss
         loss.backward()
         if dp:
             if comm_ev is not None:
@@ -568,6 +648,7 @@ def main():
         return loss
 
     comm_ev = None   # set for the communication-wait leg after the timed region
+    last_ss = [None]  # sample size of the latest training step (--dump-outputs)
 
     def fence():
         torch.cuda.synchronize()
@@ -577,6 +658,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
+    # --dump-outputs: the untimed steps between the warm-up and the timed region are not a fixed number (settling), so the
+    # training state after the warm-up is kept and put back in front of the timed steps
+    after_warmup = training_state(opt, dev) if (args.dump_outputs and opt is not None) else None
     # Settling: the first heavy process on a fresh box (or right after another GPU job) has been measured 10-20 % slow for
     # its first seconds (clocks / power state; 41.4 ms then 34.4 ms for two back-to-back runs of this script).  After the W
     # warm-up steps, up to 15 more UNTIMED steps run until two consecutive steps agree within 2 % (N > 1: five steps on every rank, the
@@ -622,6 +706,9 @@ def main():
                 continue
             if stable or settle >= 15:
                 break
+    if after_warmup is not None:
+        restore_training_state(opt, dev, after_warmup)
+        after_warmup = None
     # the model, optimizer arenas and cached workspaces are long-lived: move them out of the cyclic collector's young
     # generations so that a full collection cannot stall the launch thread for milliseconds mid-step (a training loop
     # would do the same once after its first step)
@@ -639,6 +726,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = tmax.item()
     final_loss = float(loss.float().abs().mean().item()) if extract else float(loss.item())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(loss, last_ss[0], model, extract))
     # second clock on the same build, outside the timed region: what the GPU needs for a step when the launch thread is not
     # in its way, and what the launch thread needs to enqueue one (see busy_and_enqueue)
     gpu_busy_ms, host_enq_ms = busy_and_enqueue(step) if (world == 1 and not args.no_busy) else (None, None)

@@ -627,6 +627,169 @@ def gen_mixing():
     np.savez_compressed(os.path.join(OUT, "mixing.npz"), **out)
 
 
+def gen_mixing_silent_crop():
+    """The reference measures a partner's power on the COLLATED row (after the crop, utterance_mixing_dataset.py:420-426):
+    an utterance whose kept crop is digital silence gets no SNR draw although the utterance itself is not silent.  Four
+    utterances, row 1 silent over its kept crop [0:4000] (random_crop off); mixing_prob 1 / mixing_num 3.  For numpy seeds
+    0, 1, ... up to the first one whose plan (as the product draws it) takes row 1 as a partner: the reference's collated
+    waveform batch and its next numpy draw."""
+    ref_shim.fairseq_wavlm()
+    from fairseq.data.audio import utterance_mixing_dataset as um
+    from unispeech_amd.data import UtteranceMixingCollater
+    g = torch.Generator().manual_seed(77)
+    lens = [4000, 5200, 4400, 6000]
+    audios = [torch.randn(n, generator=g) * 0.1 for n in lens]
+    audios[1][:4000] = 0.0
+    labels = [torch.randint(4, 23, (n // 320 + 1,), generator=g) for n in lens]
+    ds = object.__new__(um.UtteranceMixingDataset)
+    for k, v in dict(sample_rate=16000, label_rates=[50], pad_list=[1], eos_list=[2], num_labels=1, max_sample_size=10 ** 9,
+                     pad_audio=False, normalize=False, random_crop=False, single_target=False, multitask=False,
+                     mixing_max_len=-1, mixing_prob=1.0, mixing_num=3, mixing_noise=False, mixing_noise_prob=0.0,
+                     mixing_noise_num=1, noise_list=[], noise_container={}).items():
+        setattr(ds, k, v)
+
+    def samples():
+        return [{"id": i, "source": a.clone(), "label_list": [l.clone()], "boundary": []}
+                for i, (a, l) in enumerate(zip(audios, labels))]
+
+    out = {"in/lens": np.array(lens, dtype=np.int64)}
+    for i, (a, l) in enumerate(zip(audios, labels)):
+        out["in/audio%d" % i] = a.numpy()
+        out["in/label%d" % i] = l.numpy()
+    for seed in range(50):
+        np.random.seed(seed)
+        want = ds.collater(samples())
+        out["seed%d/next" % seed] = np.float64(np.random.random())
+        out["seed%d/source" % seed] = want["net_input"]["source"].numpy()
+        col = UtteranceMixingCollater(label_rates=[50], pad_list=[1], pad_audio=False, normalize=False, random_crop=False,
+                                      mixing_prob=1.0, mixing_num=3)
+        np.random.seed(seed)
+        ops = col.collater(samples())["mixing_plan"][0]
+        if any(int(o[1]) == 0 and int(o[2]) == 1 for o in ops):
+            out["seeds"] = np.int64(seed + 1)
+            break
+    else:
+        raise RuntimeError("no plan used the silent-crop row as a partner")
+    np.savez_compressed(os.path.join(OUT, "mixing_silent_crop.npz"), **out)
+
+
+BASE_WIDTH = dict(
+    extractor_mode="default", encoder_layers=12, encoder_embed_dim=768, encoder_ffn_embed_dim=3072,
+    encoder_attention_heads=12, activation_fn="gelu", layer_norm_first=False,
+    conv_feature_layers="[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2", conv_bias=False, feature_grad_mult=0.1,
+    dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, encoder_layerdrop=0.0, dropout_input=0.0,
+    dropout_features=0.0, mask_length=10, mask_prob=0.8, mask_selection="static", mask_other=0,
+    no_mask_overlap=False, mask_min_space=1, mask_channel_prob=0.0, conv_pos=128, conv_pos_groups=16,
+    relative_position_embedding=True, num_buckets=320, max_distance=800, gru_rel_pos=True,
+    label_rate=50, final_dim=256, logit_temp=0.1, skip_masked=False, skip_nomask=False, untie_final_proj=False,
+    target_glu=False, boundary_mask=False, expand_attention_head_size=-1,
+)
+
+
+def gen_base_width(per_tensor=64, per_logits=2048):
+    """fairseq WavLMModel + WavLMCriterion at WavLM-Base width (12 layers, d=768, head_dim 64, 320 buckets, max_distance 800;
+    2 x 5 s, row 1 padded from 70 %), the run of tests/test_oracle_vs_reference.py.  The seed-0 weights are not stored (the
+    product's constructor reproduces them, tests/test_oracle_vs_golden.py checks that): stored are the configuration, the
+    loss / sample size / accuracy counts, the padding mask, per logit matrix its shape, finiteness (packed bits), max-abs
+    over the finite entries and its values at `per_logits` fixed random positions, and per parameter the max-abs of its
+    gradient and the gradient at `per_tensor` fixed random positions (about 120 kB in all)."""
+    import json
+    WavLMModel, WavLMConfig, WavLMCriterion, _, cmi = ref_shim.fairseq_wavlm()
+    cfg = WavLMConfig()
+    for k, v in BASE_WIDTH.items():
+        setattr(cfg, k, v)
+    V, seconds = 504, 5.0
+    torch.manual_seed(0)
+    model = WavLMModel(cfg, SimpleNamespace(sample_rate=16000), [range(V)])
+    model.train()
+    crit = WavLMCriterion(SimpleNamespace(), 1.0, 0.0, loss_weights=[10.0])
+    B, T = 2, int(16000 * seconds)
+    g = torch.Generator().manual_seed(1234)
+    wav = torch.randn(B, T, generator=g)
+    pm = torch.zeros(B, T, dtype=torch.bool)
+    pm[1, int(T * 0.7):] = True
+    wav[1, int(T * 0.7):] = 0
+    target = torch.randint(4, V, (B, int(50 * seconds)), generator=g)
+    sample = {"id": torch.arange(B), "net_input": {"source": wav, "padding_mask": pm}, "target_list": [target]}
+    np.random.seed(123)
+    loss, ss, log = crit(model, sample)
+    loss.backward()
+    np.random.seed(123)
+    with torch.no_grad():
+        net = model(target_list=[target], source=wav, padding_mask=pm)
+    out = {"cfg_json": np.array(json.dumps(BASE_WIDTH)), "in/seconds": np.float64(seconds), "in/vocab": np.int64(V),
+           "out/loss": np.float64(loss.item()), "out/sample_size": np.int64(ss),
+           "out/correct_m_0": np.int64(log["correct_m_0"]), "out/count_m_0": np.int64(log["count_m_0"]),
+           "out/padding_mask": net["padding_mask"].numpy()}
+    rng = np.random.default_rng(5)
+    for key, lg in (("logit_m", net["logit_m_list"][0]), ("logit_u", net["logit_u_list"][0])):
+        fin = torch.isfinite(lg)
+        flat = lg.reshape(-1)
+        idx = np.sort(rng.choice(np.flatnonzero(fin.reshape(-1).numpy()), size=min(per_logits, int(fin.sum())),
+                                 replace=False)).astype(np.int32)
+        out["out/%s_shape" % key] = np.array(lg.shape, dtype=np.int64)
+        out["out/%s_finite" % key] = np.packbits(fin.reshape(-1).numpy())
+        out["out/%s_maxabs" % key] = np.float64(lg[fin].abs().max().item())
+        out["out/%s_idx" % key] = idx
+        out["out/%s_val" % key] = flat[torch.from_numpy(idx.astype(np.int64))].numpy()
+    # one array per field over all parameters (in named_parameters() order; `grad/count` samples each): a few members
+    # instead of three per parameter
+    names, gmax, count, gidx, gval = [], [], [], [], []
+    for n, p in model.named_parameters():
+        gr = (p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+        idx = np.sort(rng.choice(gr.numel(), size=min(per_tensor, gr.numel()), replace=False)).astype(np.int32)
+        names.append(n)
+        gmax.append(gr.abs().max().item())
+        count.append(len(idx))
+        gidx.append(idx)
+        gval.append(gr[torch.from_numpy(idx.astype(np.int64))].numpy())
+    out.update({"grad/names_json": np.array(json.dumps(names)), "grad/max": np.array(gmax, dtype=np.float64),
+                "grad/count": np.array(count, dtype=np.int64), "grad/idx": np.concatenate(gidx),
+                "grad/val": np.concatenate(gval)})
+    np.savez_compressed(os.path.join(OUT, "base_width.npz"), **out)
+
+
+LOSS_SCALER_KWARGS = (dict(), dict(init_scale=128.0, scale_window=7, tolerance=0.25),
+                      dict(init_scale=4.0, scale_window=3, threshold=1.0),
+                      dict(init_scale=2.0 ** -10, scale_window=5, min_loss_scale=1e-4))
+LOSS_SCALER_EVENTS = (1.0, 3.5, float("inf"), float("nan"), 0.1, 2.0, 9.0)
+LOSS_SCALER_ERRORS = ("OverflowError", "FloatingPointError", "ZeroDivisionError")
+
+
+def gen_loss_scaler(n_events=400):
+    """The reference's DynamicLossScaler (optim/dynamic_loss_scaler.py) on a random stream of gradient norms (random.Random(1)
+    choices from LOSS_SCALER_EVENTS) for each of LOSS_SCALER_KWARGS: after every check_overflow + update, the loss scale, the
+    iteration counter and which exception (0 = none, i = LOSS_SCALER_ERRORS[i - 1]) it raised."""
+    import importlib.util
+    import random
+    spec = importlib.util.spec_from_file_location("ref_dls", os.path.join(ref_shim.REF_ROOT, "src", "fairseq", "optim",
+                                                                           "dynamic_loss_scaler.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    out = {}
+    for c, kw in enumerate(LOSS_SCALER_KWARGS):
+        a = ref.DynamicLossScaler(**kw)
+        rnd = random.Random(1)
+        gs, scale, it, err = [], [], [], []
+        for _ in range(n_events):
+            g = rnd.choice(LOSS_SCALER_EVENTS)
+            e = 0
+            try:
+                a.check_overflow(g)
+                a.update()
+            except (OverflowError, FloatingPointError, ZeroDivisionError) as ex:
+                e = 1 + LOSS_SCALER_ERRORS.index(type(ex).__name__)
+            gs.append(g)
+            scale.append(a.loss_scale)
+            it.append(a._iter)
+            err.append(e)
+        out["case%d/grad_norm" % c] = np.array(gs, dtype=np.float64)
+        out["case%d/loss_scale" % c] = np.array(scale, dtype=np.float64)
+        out["case%d/iter" % c] = np.array(it, dtype=np.int64)
+        out["case%d/error" % c] = np.array(err, dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, "loss_scaler.npz"), **out)
+
+
 def gen_sampled_negatives():
     """wav2vec 2.0 head at function level: the reference's Wav2Vec2Model.sample_negatives and
     compute_preds called as unbound functions (they only read n_negatives / cross_sample_negatives / logit_temp), then the
@@ -680,5 +843,8 @@ if __name__ == "__main__":
     gen_tiny_w2v2()
     gen_tiny_w2v2_variants()
     gen_mixing()
+    gen_mixing_silent_crop()
+    gen_base_width()
+    gen_loss_scaler()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -232,6 +232,8 @@ def _nccl_worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    if world == 1:
+        os.environ["WAVLM_DP_FORCE"] = "1"   # a one-rank group runs the whole machinery (bench.py --force-dp)
     import torch.distributed as dist
     try:
         torch.cuda.set_device(rank)
@@ -249,6 +251,7 @@ def _nccl_worker(rank, world, port, q):
         crit = WavLMCriterion(None, 1.0, 0.0, loss_weights=[10.0], defer_logging=True)
         opt = FusedAdam(model.parameters(), model=model)
         dp = DataParallelWavLM(model, opt, bucket_bytes=4 << 20)
+        assert dp.reducer.enabled and dp.reducer.comm_stream is not None and len(dp.reducer.buckets) >= 2
         B, T = 2, 24000
         g = torch.Generator().manual_seed(100 + rank)
         wav = torch.randn(B, T, generator=g).cuda().to(torch.bfloat16)
@@ -286,15 +289,20 @@ def _nccl_worker(rank, world, port, q):
             dist.destroy_process_group()
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL over xGMI)")
+@pytest.mark.gpu
 def test_dp_world2_rccl_gradients_sum_over_ranks():
     """the real transport: one rank per GPU, backend nccl (= RCCL), bucket all-reduces on the side stream while backward
-    runs; the reduced arena must equal the sum of the ranks' local gradients"""
+    runs; the reduced arena must equal the sum of the ranks' local gradients.  Two ranks where two GPUs are visible.  RCCL
+    refuses two ranks on one device, so with one GPU the same worker runs as a one-rank RCCL group with the machinery
+    forced on (WAVLM_DP_FORCE=1, as `bench.py --force-dp`): the buckets still go through RCCL on the side stream while
+    backward runs, and the arena must come back equal to the rank's own gradient (the sum over two ranks on one GPU is
+    tests/test_dp_gpu.py, over gloo)."""
     import torch.multiprocessing as mp
+    world = min(2, torch.cuda.device_count())
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_nccl_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_nccl_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
     res = [q.get(timeout=600) for _ in procs]
@@ -417,23 +425,29 @@ def test_sat_large_remove_pretraining_modules_then_features_only():
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_on_one_gpu_over_gloo():
-    """`bench.py --gpus 8` end to end with every rank on cuda:0 and gloo as the transport (WAVLM_SHARED_GPU=1,
-    WAVLM_DIST_BACKEND=gloo): the self-launch under torch.distributed.run, the rank-count check, eight reducers issuing
+def test_bench_four_ranks_on_one_gpu_over_gloo():
+    """`bench.py --gpus 4` end to end with every rank on cuda:0 and gloo as the transport (WAVLM_SHARED_GPU=1,
+    WAVLM_DIST_BACKEND=gloo): the self-launch under torch.distributed.run, the rank-count check, four reducers issuing
     their buckets in the same order, the Trainer-order step (average, then world / sample_size) and the max-over-ranks
-    timing all run at the rank count of the 8-GPU node.  Tiny batch; the numbers mean nothing, the line must be sane."""
+    timing all run with more than two ranks.  Four, not the eight of a node: every rank opens the one GPU, and with this
+    process that stays within six processes on one GPU at a time.  Tiny batch; the numbers mean nothing, the line must be
+    sane."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WAVLM_SHARED_GPU="1", WAVLM_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--batch", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-roofline"], cwd=root, env=env, capture_output=True, text=True, timeout=1200)
+    # (--dp-alt-pass never: the alternative pass would start one more process per rank on the same GPU; the two-rank test
+    # below covers it)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--batch", "1", "--steps", "2", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-roofline", "--dp-alt-pass", "never"], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line from rank 0: " + r.stdout[-2000:]
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 8 and out["config"]["parallelism"] == "dp8" and out["config"]["global_batch"] == 8
+    assert out["n_gpus"] == 4 and out["config"]["parallelism"] == "dp4" and out["config"]["global_batch"] == 4
+    assert out["ranks_seen"] == 4 and out["distinct_devices"] == 1 and out["dist_backend"] == "gloo"
     assert out["scaling"] == "weak" and out["value"] > 0 and np.isfinite(out["final_loss"])
 
 

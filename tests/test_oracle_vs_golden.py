@@ -168,6 +168,69 @@ def test_oracle_pretrain_loss_and_grads(tiny_cfg, golden):
         assert (g - ref).abs().max().item() <= 5e-4 * max(scale, 1e-6 * gmax) + 1e-8, k
 
 
+def test_oracle_at_base_width_vs_reference_golden():
+    """WavLM-Base width (12 layers, d=768, head_dim 64, 320 buckets, max_distance 800; 2 x 5 s, row 1 padded), the run that
+    tests/test_oracle_vs_reference.py makes against the live reference, pinned by base_width.npz: the seed-0 weights of the
+    product's constructor, the oracle's loss within 1e-6 relative, the logits' shapes and finite entries exact, their max-abs
+    and their values at the stored positions within 1e-5 of that max-abs, accuracy counts exact, and every parameter's
+    gradient -- its max-abs and its values at the stored positions -- within 2e-3 of the reference's max-abs (absolute floor
+    1e-6 x the largest gradient for the analytically-zero k_proj.bias gradients)."""
+    import json
+    from types import SimpleNamespace
+    z = load_golden("base_width.npz")
+    base = json.loads(str(z["cfg_json"]))
+    V, seconds = int(z["in/vocab"]), float(z["in/seconds"])
+    cfg = WavLMPretrainConfig(**{k: v for k, v in base.items() if k in WavLMPretrainConfig.__dataclass_fields__})
+    torch.manual_seed(0)
+    sd = {k: v.detach().clone().requires_grad_(v.is_floating_point())
+          for k, v in WavLMPretrainModel(cfg, None, [range(V)]).state_dict().items()}
+    names = json.loads(str(z["grad/names_json"]))
+    assert set(names) == {k for k, v in sd.items() if v.is_floating_point()}
+    B, T = 2, int(16000 * seconds)
+    g = torch.Generator().manual_seed(1234)
+    wav = torch.randn(B, T, generator=g)
+    pm = torch.zeros(B, T, dtype=torch.bool)
+    pm[1, int(T * 0.7):] = True
+    wav[1, int(T * 0.7):] = 0
+    target = torch.randint(4, V, (B, int(50 * seconds)), generator=g)
+    ocfg = SimpleNamespace(**base)
+    Tp = T
+    for _, k, s_ in eval(base["conv_feature_layers"]):
+        Tp = (Tp - k) // s_ + 1
+    fpm = O.forward_padding_mask(Tp, pm)
+    assert torch.equal(fpm, torch.from_numpy(z["out/padding_mask"]))
+    np.random.seed(123)
+    m = masking.compute_mask_indices((B, Tp), fpm, base["mask_prob"], base["mask_length"], base["mask_selection"],
+                                     base["mask_other"], min_masks=2, no_overlap=False, min_space=1)
+    net = O.pretrain_forward(sd, ocfg, wav, [target], pm, torch.from_numpy(m), [V])
+    loss, ss, log = O.criterion(net, 1.0, 0.0, [10.0])
+    loss.backward()
+    assert ss == int(z["out/sample_size"])
+    assert abs(loss.item() - float(z["out/loss"])) <= 1e-6 * abs(float(z["out/loss"])), (loss.item(), float(z["out/loss"]))
+    for a, key in ((net["logit_m_list"][0].detach(), "out/logit_m"), (net["logit_u_list"][0].detach(), "out/logit_u")):
+        assert tuple(a.shape) == tuple(z[key + "_shape"]), key
+        fin = torch.isfinite(a)
+        assert np.array_equal(np.packbits(fin.reshape(-1).numpy()), z[key + "_finite"]), key
+        ref_max = float(z[key + "_maxabs"])
+        assert abs(a[fin].abs().max().item() - ref_max) < 1e-5 * ref_max, key
+        got = a.reshape(-1)[torch.from_numpy(z[key + "_idx"].astype(np.int64))]
+        assert ((got - torch.from_numpy(z[key + "_val"])).abs().max() / ref_max).item() < 1e-5, key
+    assert log["correct_m_0"] == int(z["out/correct_m_0"]) and log["count_m_0"] == int(z["out/count_m_0"])
+    gmax = float(z["grad/max"].max())
+    ends = np.cumsum(z["grad/count"])
+    bad = []
+    for n, ref_max, lo, hi in zip(names, z["grad/max"], ends - z["grad/count"], ends):
+        p = sd[n]
+        og = (p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+        if n.startswith("feature_extractor."):
+            og = og * base["feature_grad_mult"]   # GradMultiply (wavlm.py:479): the oracle returns the unscaled gradient
+        got = og[torch.from_numpy(z["grad/idx"][lo:hi].astype(np.int64))]
+        e = max((got - torch.from_numpy(z["grad/val"][lo:hi])).abs().max().item(), abs(og.abs().max().item() - ref_max))
+        if e > 2e-3 * ref_max + 1e-6 * gmax:
+            bad.append((n, e, float(ref_max)))
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("golden", ["tiny_large.npz", "tiny_large_convbias.npz"])
 def test_oracle_large_structure(golden):
     """extractor_mode 'layer_norm' + layer_norm_first (WavLM-Large structure, BASELINE.json configs[3]) against the

@@ -7,7 +7,8 @@ is modified) at that width with a padded row and compares loss, logits and every
 oracle/wavlm_oracle.py.  It also pins `adam_reference_step` + the clip rule against the reference's `Adam`,
 `clip_grad_norm_` and the `_multiply_factor` semantics of its fp16/bf16 optimizer wrapper.
 
-Skipped where /root/reference does not exist (the GPU box): there the committed goldens are the pin.
+Skipped where /root/reference does not exist (the GPU box): there the committed goldens are the pin, the Base-width run
+included (tests/golden/base_width.npz, test_oracle_vs_golden.py::test_oracle_at_base_width_vs_reference_golden).
 """
 import os
 import sys
