@@ -3,6 +3,7 @@
 bf16, 32 x 15 s utterances per GPU, masked-prediction loss, forward + backward + gradient reduction + fused Adam.
 
     python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full   # the same headline + every diagnostic leg (below)
     python bench.py --gpus N ...                        # no launcher: re-executes itself under torch.distributed.run
     python bench.py --config large ...                  # WavLM-Large, 20 s utterances (configs[3] per-GPU slice)
     python bench.py --config extract ...                # eval `extract_features` per call, 32 x 15 s
@@ -11,11 +12,17 @@ bf16, 32 x 15 s utterances per GPU, masked-prediction loss, forward + backward +
 
 Synthetic data of the real shape (randn waveform, random k-means labels), random-init weights of the real
 architecture; recipe dropouts on (dropout 0.1, attention_dropout 0.1, dropout_input 0.1), layerdrop 0 (no layer is
-ever skipped inside the timed region).  Rank 0 prints ONE JSON line.  Extra legs outside the timed region:
-`roofline` (HIP-event timing of every bf16 MFMA GEMM launch during two extra steps; `roofline.kernels` carries the same
-live measurement for the fused attention forward / backward (MFMA-bound), the conv0 stage and the LayerNorm row kernels
-(HBM-bound)) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded 1 x 15 s sample, thread count chosen
-by a sweep on the sample itself; rank 0, N=1 only).
+ever skipped inside the timed region).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the untimed settling steps (K steps,
+then until two consecutive steps agree), the K timed steps, `--dump-outputs` if given, the line. `--full` adds every
+other leg, all outside the timed region: `ms_per_step_unsettled` (the time of the first K settling steps),
+`gpu_busy_ms_per_step` / `host_enqueue_ms_per_step`, `roofline` (HIP-event timing of every bf16 MFMA GEMM launch during
+extra steps; `roofline.kernels` carries the same live measurement for the fused attention forward / backward
+(MFMA-bound), the conv0 stage and the LayerNorm row kernels (HBM-bound)), `cpu_baseline` (the CPU oracle timed on the
+host cores on a bounded 1 x 15 s sample, thread count chosen by a sweep on the sample itself; rank 0, N=1 only),
+`secondary` (config base, N=1) and, for data-parallel runs, the `data_parallel` block with its alternative passes. The
+`--no-*` switches take single legs out of a `--full` run.
 """
 import argparse
 import json
@@ -247,7 +254,7 @@ def live_gemm_traffic(args):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, ctr)
             cmd = [exe, "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-settle", "--no-busy", "--no-cpu-baseline", "--no-roofline", "--no-secondary",
+                   os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-settle",   # a plain run: no other leg
                    "--config", args.config, "--batch", str(args.batch)]
             r = subprocess.run(cmd, env=env, cwd="/tmp", capture_output=True, text=True, timeout=300)
             files = glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True)
@@ -277,13 +284,14 @@ def live_gemm_traffic(args):
 
 
 def secondary_lines(configs=("large", "extract"), steps=5, warmup=2):
-    """{config: {ms_per_step, value, unit, frac, ...}}: `bench.py --config <c> --steps 5 --warmup 2` in a fresh process each
-    (a crash or time-out there is reported under the config's name and cannot take the headline down)"""
+    """{config: {ms_per_step, value, unit, frac, ...}}: `bench.py --config <c> --steps 5 --warmup 2 --full` without its CPU
+    baseline and clocks legs, in a fresh process each (a crash or time-out there is reported under the config's name and
+    cannot take the headline down)"""
     import subprocess
     res = {}
     for c in configs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-busy", "--no-secondary"]
+               "--full", "--no-cpu-baseline", "--no-busy", "--no-secondary"]
         t0 = time.time()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -385,7 +393,7 @@ def run_alt_pass(args, rank, world, dev, native=False):
     else:
         env.update(WAVLM_DP_RESERVED_CUS="0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--batch", str(args.batch), "--config", args.config, "--dp-alt-pass", "never", "--no-cpu-baseline", "--no-roofline"]
+           "--batch", str(args.batch), "--config", args.config, "--full", "--dp-alt-pass", "never", "--no-cpu-baseline", "--no-roofline"]
     torch.cuda.synchronize()
     res = {"settings": {"WAVLM_DP_NATIVE": 1, "NCCL_MAX_NCHANNELS": env.get("NCCL_MAX_NCHANNELS")} if native
            else {"NCCL_MAX_NCHANNELS": None, "WAVLM_DP_RESERVED_CUS": 0}}
@@ -498,22 +506,28 @@ def main():
                     help="base = BASELINE.json configs[1] (the headline); large = WavLM-Large, 20 s utterances; "
                          "sat_large = UniSpeech-SAT Large with utterance mixing + contrastive head; extract = eval "
                          "extract_features per call on the configs[1] batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="report / run every leg besides the headline (ms_per_step_unsettled, gpu_busy / host_enqueue, "
+                         "roofline, cpu_baseline, secondary, the data_parallel block and its alternative passes), all outside "
+                         "the timed steps; without it a run sets up, warms up, settles, times the steps, dumps if asked and "
+                         "prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--no-settle", action="store_true", help="skip the untimed settling steps after the warm-up")
-    ap.add_argument("--no-busy", action="store_true", help="skip the gpu_busy / host_enqueue leg (profiler passes: only the timed steps run)")
+    ap.add_argument("--no-busy", action="store_true", help="--full without the gpu_busy / host_enqueue leg")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` leg (default flags, N = 1, config base: 5 steps each of --config large and --config "
+                    help="--full without the `secondary` leg (N = 1, config base: 5 steps each of --config large and --config "
                          "extract in fresh processes on the same GPU after the headline is taken)")
     ap.add_argument("--live-traffic", action="store_true",
-                    help="collect roofline.traffic live (two rocprofv3 PMC passes of this command as subprocesses, ~1 min)")
+                    help="with --full: collect roofline.traffic live (two rocprofv3 PMC passes of this command as subprocesses, ~1 min)")
     ap.add_argument("--dp-alt-pass", choices=["auto", "always", "never"], default="auto",
-                    help="N > 1: second measurement with NCCL_MAX_NCHANNELS unset and no reserved CUs (fresh processes on the same "
-                         "GPUs); auto = when a rank waits > 1 ms for the gradient all-reduce after backward")
+                    help="N > 1, with --full: second measurement with NCCL_MAX_NCHANNELS unset and no reserved CUs (fresh processes "
+                         "on the same GPUs); auto = when a rank waits > 1 ms for the gradient all-reduce after backward")
     ap.add_argument("--force-dp", action="store_true",
                     help="1 GPU: run the step through the data-parallel machinery of a rank (DataParallelWavLM over a one-rank gloo "
                          "group: bucketed reducer on its side stream, gradient listeners, reserved CUs, the sample-size all-reduce) -- "
-                         "what the N > 1 path costs a rank before any byte crosses a link; the line carries a `data_parallel` block")
+                         "what the N > 1 path costs a rank before any byte crosses a link; with --full the line carries a "
+                         "`data_parallel` block")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
                          "at most 64 MB in all): training configs the loss, the sample size and, per parameter, a fixed seeded "
@@ -526,6 +540,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.live_traffic or args.dp_alt_pass == "always"):
+        ap.error("--live-traffic and --dp-alt-pass always belong to legs that only --full runs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rendezvous on 127.0.0.1),
@@ -669,14 +685,17 @@ def main():
     settle_host_ms = None
     unsettled_ms = None
     if not args.no_settle and world == 1:
-        # the r02 methodology (no settling steps): the first K steps right after the warm-up, timed the same way, reported
-        # next to the headline as `ms_per_step_unsettled` so that rounds stay comparable like for like
+        # K steps right after the warm-up, in front of the settling loop.  Every run takes them: they are part of what
+        # precedes the timed region (without them the timed steps measured ~0.35 % slower, 33.65 against 33.53 ms, same
+        # box, alternating runs).  --full also reports their time as `ms_per_step_unsettled`, the r02 methodology (no
+        # settling steps), so that rounds stay comparable like for like
         torch.cuda.synchronize()
         tu = time.perf_counter()
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
-        unsettled_ms = (time.perf_counter() - tu) / args.steps * 1e3
+        if args.full:
+            unsettled_ms = (time.perf_counter() - tu) / args.steps * 1e3
     if not args.no_settle and world > 1:
         for _ in range(5):  # a fixed count: every rank must run the same number of (collective) steps
             step()
@@ -730,12 +749,28 @@ def main():
         write_outputs(args.dump_outputs, step_outputs(loss, last_ss[0], model, extract))
     # second clock on the same build, outside the timed region: what the GPU needs for a step when the launch thread is not
     # in its way, and what the launch thread needs to enqueue one (see busy_and_enqueue)
-    gpu_busy_ms, host_enq_ms = busy_and_enqueue(step) if (world == 1 and not args.no_busy) else (None, None)
+    gpu_busy_ms, host_enq_ms = busy_and_enqueue(step) if (args.full and world == 1 and not args.no_busy) else (None, None)
     dp_info = None
     if dp:
+        # what identifies the run as N ranks on N distinct devices over RCCL (no step: one collective after the timed region)
+        props = torch.cuda.get_device_properties(dev)
+        ident = "%s|%s" % (getattr(props, "uuid", None), getattr(props, "pci_bus_id", local_rank))
+        gathered = [None] * world
+        dist.all_gather_object(gathered, {"rank": rank, "device": ident, "pinned": pinned})
+        gathered.sort(key=lambda g_: g_["rank"])
+        try:
+            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
+        except Exception:
+            rccl = None
+        dp_info = {"ranks_seen": len(gathered), "distinct_devices": len({g_["device"] for g_ in gathered}),
+                   "backend": backend, "rccl_version": rccl,
+                   # "torch": torch.distributed collectives on a side stream; "native": the library's own RCCL reducer
+                   # (wavlm_dp_*, WAVLM_DP_NATIVE=1; no per-bucket events: buckets_rank0 is null then)
+                   "transport": "native" if net.reducer.transport is not None else "torch",
+                   "host_cores_per_rank": [g_["pinned"] for g_ in gathered]}
+    if dp and args.full:
         # evidence for the overlap of the gradient all-reduce with backward, from the driver's own run: per rank, the time
-        # the compute stream waits between the end of backward and the completion of the last bucket (0 = fully hidden),
-        # plus what identifies the run as N distinct devices over RCCL
+        # the compute stream waits between the end of backward and the completion of the last bucket (0 = fully hidden)
         waits = []
         comm_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         for _ in range(3):
@@ -768,31 +803,20 @@ def main():
                 exposed_last = max(0.0, bucket_rows[-1]["ends_ms_after_backward_end"])
         comm_ev = None
         waits.sort()
-        props = torch.cuda.get_device_properties(dev)
-        ident = "%s|%s" % (getattr(props, "uuid", None), getattr(props, "pci_bus_id", local_rank))
-        gathered = [None] * world
-        dist.all_gather_object(gathered, {"rank": rank, "device": ident, "comm_wait_ms": round(waits[1], 3), "pinned": pinned})
-        try:
-            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
-        except Exception:
-            rccl = None
-        dp_info = {"ranks_seen": len(gathered), "distinct_devices": len({g_["device"] for g_ in gathered}),
-                   "backend": backend, "rccl_version": rccl, "buckets": len(red.buckets),
-                   "bucket_mib": round(net._bucket_bytes / 2 ** 20, 1), "reserved_cus": ops.get_reserved_cus(),
-                   "grad_arena_mib": round(opt.flat_grad.numel() * opt.flat_grad.element_size() / 2 ** 20, 1),
-                   "grad_sum_dtype": str(opt.flat_grad.dtype).replace("torch.", ""),
-                   "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS"),
-                   # "torch": torch.distributed collectives on a side stream; "native": the library's own RCCL reducer
-                   # (wavlm_dp_*, WAVLM_DP_NATIVE=1; no per-bucket events: buckets_rank0 is null then)
-                   "transport": "native" if red.transport is not None else "torch",
-                   # (rank 0's view, median of three diagnostic steps; bus_gb_s = bytes x 2 (N - 1) / N / time: compare with one
-                   # xGMI link, ~153 GB/s -- the cap NCCL_MAX_NCHANNELS = reserved CUs is a hypothesis)
-                   "buckets_rank0": bucket_rows, "exposed_ms_last_bucket_rank0": exposed_last,
-                   "allreduce_bus_gb_s_rank0": None if not bucket_rows else round(
-                       sum(r_["mib"] for r_ in bucket_rows) * 2 ** 20 * (2.0 * (world - 1) / world)
-                       / max(sum(r_["allreduce_ms"] for r_ in bucket_rows), 1e-6) / 1e6, 1),
-                   "comm_wait_ms_per_rank": [g_["comm_wait_ms"] for g_ in sorted(gathered, key=lambda g_: g_["rank"])],
-                   "host_cores_per_rank": [g_["pinned"] for g_ in sorted(gathered, key=lambda g_: g_["rank"])]}
+        waits_all = [None] * world
+        dist.all_gather_object(waits_all, round(waits[1], 3))
+        dp_info.update({"buckets": len(red.buckets),
+                        "bucket_mib": round(net._bucket_bytes / 2 ** 20, 1), "reserved_cus": ops.get_reserved_cus(),
+                        "grad_arena_mib": round(opt.flat_grad.numel() * opt.flat_grad.element_size() / 2 ** 20, 1),
+                        "grad_sum_dtype": str(opt.flat_grad.dtype).replace("torch.", ""),
+                        "rccl_max_nchannels": os.environ.get("NCCL_MAX_NCHANNELS"),
+                        # (rank 0's view, median of three diagnostic steps; bus_gb_s = bytes x 2 (N - 1) / N / time: compare with
+                        # one xGMI link, ~153 GB/s -- the cap NCCL_MAX_NCHANNELS = reserved CUs is a hypothesis)
+                        "buckets_rank0": bucket_rows, "exposed_ms_last_bucket_rank0": exposed_last,
+                        "allreduce_bus_gb_s_rank0": None if not bucket_rows else round(
+                            sum(r_["mib"] for r_ in bucket_rows) * 2 ** 20 * (2.0 * (world - 1) / world)
+                            / max(sum(r_["allreduce_ms"] for r_ in bucket_rows), 1e-6) / 1e6, 1),
+                        "comm_wait_ms_per_rank": waits_all})
 
     # N > 1, self-diagnosis on the first real node (nobody could tune this beforehand: RCCL has never executed in the build
     # environment): when a rank waits noticeably for the all-reduce after backward -- or on request -- the same measurement
@@ -800,7 +824,7 @@ def main():
     # (RCCL picks its own channel count) and no CUs reserved (full persistent grids).  Fresh processes, because RCCL reads
     # its environment once per process.  Both results go into `data_parallel`; the headline stays the default configuration's.
     alt = None
-    if world > 1 and dp_info is not None and args.dp_alt_pass != "never":
+    if args.full and world > 1 and dp_info is not None and args.dp_alt_pass != "never":
         worst_wait = max(dp_info["comm_wait_ms_per_rank"])
         if args.dp_alt_pass == "always" or worst_wait > 1.0:
             alt = run_alt_pass(args, rank, world, dev)
@@ -814,7 +838,7 @@ def main():
                 dp_info["alt_pass_native"] = alt_native
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # Three single-step passes, the one with the smallest GEMM time is reported.  The events bracket each launch ON THE
         # STREAM; with the events' own host cost the launch thread runs level with the GPU, so one of the HIP runtime's
         # periodic launch stalls (tens of ms every ~2000 launches on these boxes) lands between an event and its kernel
@@ -924,18 +948,19 @@ def main():
             n_ = dp_info.get("alt_pass_native")
             if n_ and n_.get("value"):
                 dp_info["alt_pass_native_faster_than_default"] = bool(n_["value"] > 1.01 * value)
-            out["data_parallel"] = dp_info
+            if args.full:
+                out["data_parallel"] = dp_info
         if roof is not None:
             out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline and args.config == "base":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "base":
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.no_cpu_baseline and extract:
+        if args.full and world == 1 and not args.no_cpu_baseline and extract:
             out["cpu_baseline"] = cpu_baseline_extract()
-        if (world == 1 and args.config == "base" and args.batch == BATCH_PER_GPU and not args.no_secondary
+        if (args.full and world == 1 and args.config == "base" and args.batch == BATCH_PER_GPU and not args.no_secondary
                 and args.reserved_cus < 0):
-            # the driver only ever runs the default command, so two of the five BASELINE configs would never get a
-            # driver-observed number: the headline is complete at this point (nothing below touches its timed region); the
-            # model and its arenas are released and the other configs run as ordinary short bench.py runs on the same GPU
+            # two more of the five BASELINE configs in the same line: the headline is complete at this point (nothing below
+            # touches its timed region); the model and its arenas are released and the other configs run as ordinary short
+            # bench.py runs on the same GPU
             del sample, wav, crit, net, opt, model
             gc.collect()
             torch.cuda.empty_cache()

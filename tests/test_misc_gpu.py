@@ -453,7 +453,7 @@ def test_bench_four_ranks_on_one_gpu_over_gloo():
 
 @pytest.mark.gpu
 def test_bench_data_parallel_self_diagnosis_and_alternative_pass():
-    """The first run on a real multi-GPU node has to explain itself: `bench.py --gpus 2` prints, per
+    """The first run on a real multi-GPU node has to explain itself: `bench.py --gpus 2 --full` prints, per
     gradient bucket, when its all-reduce was launched relative to the end of backward, how long it took, its bus bandwidth
     and what the last bucket leaves exposed -- and (here forced with --dp-alt-pass always, on a node: whenever a rank waits
     > 1 ms) repeats the measurement in fresh processes with NCCL_MAX_NCHANNELS unset and no CUs reserved, printing both in
@@ -464,7 +464,7 @@ def test_bench_data_parallel_self_diagnosis_and_alternative_pass():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WAVLM_SHARED_GPU="1", WAVLM_DIST_BACKEND="gloo", WAVLM_DP_BUCKET_MIB="32")
     env.pop("NCCL_MAX_NCHANNELS", None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--batch", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--batch", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-roofline", "--dp-alt-pass", "always"], cwd=root, env=env, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -495,7 +495,7 @@ def test_bench_force_dp_prices_the_data_parallel_machinery_on_one_gpu():
     reserved in every persistent GEMM grid, NCCL_MAX_NCHANNELS capped, the sample-size all-reduce.  Its ms_per_step must stay
     within 4 % of the plain `--gpus 1` path on the same box (the reservation alone was measured at +0.5 %,
     profiles/r04/reserved_cus_*.txt; run-to-run noise of two short runs ~1 %), the loss must be the same number, and the line
-    carries the `data_parallel` block a node run prints."""
+    of --full carries the `data_parallel` block a node run prints."""
     import json
     import subprocess
     import sys
@@ -505,8 +505,9 @@ def test_bench_force_dp_prices_the_data_parallel_machinery_on_one_gpu():
         env.pop(k, None)
     out = {}
     for tag, extra in (("plain", []), ("dp", ["--force-dp"])):
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-roofline",
-                            "--no-secondary", "--no-busy", "--no-settle"] + extra, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline",
+                            "--no-roofline", "--no-secondary", "--no-busy", "--no-settle"] + extra, cwd=root, env=env,
+                           capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, r.stdout[-2000:]
@@ -522,3 +523,30 @@ def test_bench_force_dp_prices_the_data_parallel_machinery_on_one_gpu():
     assert dp["buckets_rank0"] and all(r_["allreduce_ms"] > 0 for r_ in dp["buckets_rank0"])
     assert abs(a["final_loss"] - b["final_loss"]) <= 2e-3 * abs(a["final_loss"])   # same seeds, same step: sums of one rank
     assert b["ms_per_step"] <= 1.04 * a["ms_per_step"], (a["ms_per_step"], b["ms_per_step"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_only():
+    """A plain `bench.py --gpus 1` run sets up, warms up, settles, times its steps and prints the line: nothing that
+    `--full` adds (ms_per_step_unsettled, gpu_busy / host_enqueue, roofline, cpu_baseline, secondary) is in it, and the
+    headline fields are all there."""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 2
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)], cwd=root,
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    print("plain run: %.1f s of wall, %.1f s outside the warm-up and timed steps" % (wall, wall - (steps + warmup) * out["ms_per_step"] / 1e3))
+    assert out["steps"] == steps and out["warmup"] == warmup and out["n_gpus"] == 1
+    assert out["unit"] == "audio-s/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["ms_per_step"] > 0 and out["value"] > 0 and out["settle_steps"] >= 1
+    assert out["gpu_busy_ms_per_step"] is None and out["host_enqueue_ms_per_step"] is None and out["ms_per_step_unsettled"] is None
+    assert not {"roofline", "cpu_baseline", "secondary", "data_parallel"} & set(out)
