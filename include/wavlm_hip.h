@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 21
+#define WAVLM_HIP_ABI_VERSION 22
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -481,6 +481,38 @@ int wavlm_dp_init(int32_t rank, int32_t world, const void* id128, int32_t averag
 int wavlm_dp_bucket_ready(void* base, uint64_t count, int32_t dtype, void* compute_stream);
 int wavlm_dp_finish(void* compute_stream);
 int wavlm_dp_destroy(void);
+
+/* ------------------------------------------------------------------------------------------
+ * k-means (ABI 22, csrc/kmeans.hip): HuBERT / WavLM pre-training targets on the device.  Replaces the CPU work of
+ * src/examples/hubert/simple_kmeans/dump_km_label.py:25-47 (ApplyKmeans: argmin(|x|^2 - 2 x.C + |c|^2)) and
+ * learn_kmeans.py:24-47 (sklearn MiniBatchKMeans: the assignment and centre-update steps; the loop is host code,
+ * unispeech_amd/kmeans.py).
+ *   wavlm_kmeans_centres_bytes(K, D)      bytes of the prepared centre image: fp32 [Kp, Dp] (K rounded up to 64, D to 32,
+ *                                         zero padded) followed by Cnorm fp32 [Kp]
+ *   wavlm_kmeans_prepare(C, K, D, ...)    fp32 centres C [K, D] -> image; Cnorm_j = one fmaf chain over d in order.  Once
+ *                                         per set of centres.
+ *   wavlm_kmeans_assign                   X [N, D] (x_dtype WL_F32 / WL_BF16, row stride ldx >= D) against the image:
+ *                                         labels int32 [N] = argmin_j (Cnorm_j - 2 x.c_j) through fp32 MFMA (exact fmaf
+ *                                         chains); ties go to the LOWEST index (numpy / torch argmin).  min_dist (fp32 [N],
+ *                                         optional) = |x - c_label|^2 summed as squared differences.  No distance matrix is
+ *                                         written.  Any N, K, D >= 1.
+ *   wavlm_kmeans_accumulate               sums fp32 [K, D] and counts int32 [K] of the rows per label (labels outside
+ *                                         [0, K) are ignored): stable inverted index + bounded chunks summed in row order,
+ *                                         then chunk partials in chunk order -- bitwise reproducible, no float atomics.
+ *                                         workspace >= wavlm_kmeans_accumulate_workspace_bytes(N, K, D); N < 2^31.
+ *   wavlm_kmeans_update                   mode 0 (Lloyd): c_j = sums_j / n_j; mode 1 (mini-batch, sklearn
+ *                                         _minibatch_update_dense): c_j = (c_j w_j + sums_j) * (1 / (w_j + n_j)),
+ *                                         w_j += n_j.  Clusters with n_j == 0 keep their centre (and weight) in both modes.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t wavlm_kmeans_centres_bytes(int32_t K, int32_t D);
+int wavlm_kmeans_prepare(const float* C, int32_t K, int32_t D, void* image, uint64_t image_bytes, void* stream);
+int wavlm_kmeans_assign(const void* X, int32_t x_dtype, int64_t N, int32_t D, int64_t ldx, const void* image, int32_t K,
+                        int32_t* labels, float* min_dist, void* stream);
+uint64_t wavlm_kmeans_accumulate_workspace_bytes(int64_t N, int32_t K, int32_t D);
+int wavlm_kmeans_accumulate(const void* X, int32_t x_dtype, int64_t N, int32_t D, int64_t ldx, const int32_t* labels,
+                            int32_t K, float* sums, int32_t* counts, void* workspace, uint64_t ws_bytes, void* stream);
+int wavlm_kmeans_update(float* C, float* weights, const float* sums, const int32_t* counts, int32_t K, int32_t D,
+                        int32_t mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
