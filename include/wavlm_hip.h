@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 22
+#define WAVLM_HIP_ABI_VERSION 23
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -513,6 +513,59 @@ int wavlm_kmeans_accumulate(const void* X, int32_t x_dtype, int64_t N, int32_t D
                             int32_t K, float* sums, int32_t* counts, void* workspace, uint64_t ws_bytes, void* stream);
 int wavlm_kmeans_update(float* C, float* weights, const float* sums, const int32_t* counts, int32_t K, int32_t D,
                         int32_t mode, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * speaker head (ABI 23, csrc/spkhead.hip): the inference path of the reference's ECAPA-TDNN over upstream layer states,
+ * downstreams/speaker_verification/models/ecapa_tdnn.py.  Its k = 5 and 1x1 convolutions and its Linear are wavlm_gemm calls
+ * (overlapping rows over a time-padded channel-last tensor for k = 5); these entry points are everything in between.
+ * All tensors channel-last [B, T, C] with a batch stride and a row stride (in elements), WL_F32 or WL_BF16; arithmetic,
+ * statistics and softmax in fp32.  `lengths` (int32 [B], device, optional): frames t >= lengths[b] do not exist for
+ * utterance b -- they are written as zeros and left out of every mean / norm / pooling; NULL = all T frames.
+ * Nothing is reduced across workgroups: results are bitwise reproducible.
+ *   wavlm_spk_mix_norm     ecapa_tdnn.py:261-270 (torch.stack of the states, softmax-weighted sum, transpose, + 1e-6,
+ *                          InstanceNorm1d): out[b, t, :] = ((sum_l weights[l] * state_l[b, t, :] + add) - mean) * rstd, mean
+ *                          and biased variance per (b, channel) over the valid frames.  `states`, `stride_b`, `stride_t`
+ *                          are HOST arrays of n_states <= 32 device pointers / element strides (unit channel stride; the
+ *                          tensors are read where extract_features left them); `weights` fp32 [n_states] on the device (the
+ *                          softmax already applied).  Every state is read once for T <= 1024 (the mixed slab stays in LDS);
+ *                          later frames are mixed three times.  Rows [-pad, 0) and [T, T + pad) of every utterance of `out`
+ *                          are written as zeros (the k = 5 convolution's padding): `out` points at row 0.
+ *   wavlm_spk_rowact       ecapa_tdnn.py:63-64 / :282 / :154: y = act(x) * scale[c] + shift[c], act 0 = ReLU, 1 = tanh,
+ *                          2 = none; scale / shift fp32 [C] (BatchNorm folded: w / sqrt(var + eps), b - mean * scale) or
+ *                          NULL.  mean_out (fp32 [B, C], optional) receives the time mean of y over the valid frames
+ *                          (SE_Connect's x.mean(dim=2), :78) from the same pass.  x == y is allowed.
+ *   wavlm_spk_res2         ecapa_tdnn.py:34-50 (Res2Conv1dReluBn, scale 8, width 64: C must be 512), one launch: y[:, :, 64 i
+ *                          : 64 i + 64] = BN_i(relu(conv_i(sp_i))), sp_0 = x_0, sp_i = y_{i-1} + x_i, kernel 3, `dilation`
+ *                          (1..4) with zero padding; the eighth split is copied.  w_image fp32 [7][3 taps][64 in][64 out],
+ *                          bias / scale / shift fp32 [7][64].  Each workgroup recomputes a halo of 7 * dilation frames per
+ *                          side.  bf16 x: the steps run on bf16 MFMA (the running tensor rounded to bf16 as the operand
+ *                          only; accumulation, running add and affine in fp32); fp32 x: fp32 FMA throughout.  x != y.
+ *   wavlm_spk_se_residual  ecapa_tdnn.py:77-83,125: out = x * sigmoid(W2 relu(W1 mean + b1) + b2) + res; W1 [Cb, C], W2
+ *                          [C, Cb] and the biases in w_dtype; workspace >= wavlm_spk_se_workspace_bytes(B, C).
+ *   wavlm_spk_asp          ecapa_tdnn.py:156-160,283: alpha = softmax over time of `logits` per channel; mean = sum alpha x,
+ *                          std = sqrt(max(sum alpha x^2 - mean^2, 1e-9)); one pass, alpha is never written.  pooled_raw
+ *                          (fp32 [B, 2 C], optional) = [mean | std]; out (optional) = the same times scale + shift (fp32
+ *                          [2 C], the BatchNorm that follows; NULL = identity).
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_spk_mix_norm(const void* const* states, const int64_t* stride_b, const int64_t* stride_t, int32_t n_states,
+                       int32_t dtype, const float* weights, const int32_t* lengths, int32_t B, int32_t T, int32_t D,
+                       void* out, int32_t out_dtype, int64_t out_stride_b, int64_t out_stride_t, int32_t pad, float add,
+                       float eps, void* stream);
+int wavlm_spk_rowact(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t ldx, void* y, int32_t y_dtype,
+                     int64_t y_stride_b, int64_t ldy, int32_t B, int32_t T, int32_t C, int32_t act, const float* scale,
+                     const float* shift, const int32_t* lengths, float* mean_out, void* stream);
+int wavlm_spk_res2(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t ldx, void* y, int32_t y_dtype,
+                   int64_t y_stride_b, int64_t ldy, int32_t B, int32_t T, int32_t C, int32_t dilation, const float* w_image,
+                   const float* bias, const float* scale, const float* shift, const int32_t* lengths, void* stream);
+uint64_t wavlm_spk_se_workspace_bytes(int32_t B, int32_t C);
+int wavlm_spk_se_residual(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t ldx, const float* mean, const void* w1,
+                          const void* b1, const void* w2, const void* b2, int32_t w_dtype, const void* res, int32_t res_dtype,
+                          int64_t res_stride_b, int64_t ld_res, void* out, int32_t out_dtype, int64_t out_stride_b,
+                          int64_t ld_out, int32_t B, int32_t T, int32_t C, int32_t Cb, const int32_t* lengths,
+                          void* workspace, uint64_t ws_bytes, void* stream);
+int wavlm_spk_asp(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t ldx, const void* logits, int32_t l_dtype,
+                  int64_t l_stride_b, int64_t ldl, int32_t B, int32_t T, int32_t C, const int32_t* lengths, const float* scale,
+                  const float* shift, float* pooled_raw, void* out, int32_t out_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVLM_HIP_LIB") or os.path.join(_HERE, "lib", "libwavlm_hip.so")
 
 _lib = None
-ABI_VERSION = 22  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
+ABI_VERSION = 23  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
 
 F32, BF16 = 0, 1
 
@@ -176,6 +176,17 @@ SIGNATURES = {
     "wavlm_kmeans_accumulate_workspace_bytes": (c_u64, [c_i64, c_i32, c_i32]),
     "wavlm_kmeans_accumulate": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_kmeans_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "wavlm_spk_mix_norm": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i64, c_i64,
+                                   c_i32, c_f32, c_f32, c_vp]),
+    "wavlm_spk_rowact": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp]),
+    "wavlm_spk_res2": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                               c_vp, c_vp, c_vp, c_vp]),
+    "wavlm_spk_se_workspace_bytes": (c_u64, [c_i32, c_i32]),
+    "wavlm_spk_se_residual": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64,
+                                      c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_u64, c_vp]),
+    "wavlm_spk_asp": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_i32, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),
