@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 23
+#define WAVLM_HIP_ABI_VERSION 24
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -566,6 +566,42 @@ int wavlm_spk_se_residual(const void* x, int32_t x_dtype, int64_t x_stride_b, in
 int wavlm_spk_asp(const void* x, int32_t x_dtype, int64_t x_stride_b, int64_t ldx, const void* logits, int32_t l_dtype,
                   int64_t l_stride_b, int64_t ldl, int32_t B, int32_t T, int32_t C, const int32_t* lengths, const float* scale,
                   const float* shift, float* pooled_raw, void* out, int32_t out_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * diarization head (ABI 24, csrc/diar.hip): the inference path of the reference's EEND-vector-clustering model over upstream
+ * layer states, downstreams/speaker_diarization/models/models.py and models/transformer.py.  Its Linear layers are wavlm_gemm
+ * calls and its LayerNorms wavlm_layernorm_fwd calls (the residual operand carries `e + att(e)` / `e + ff(e)`); these entry
+ * points are the three steps in between.  Tensors WL_F32 or WL_BF16; arithmetic, statistics and softmax in fp32.  Nothing is
+ * reduced across workgroups: results are bitwise reproducible and no chunk depends on the batch it is in.
+ *   wavlm_diar_front      models.py:210-225 with context_size 0.  mixed[b, t, c] = sum_l weights[l] * state_l[b, t, c] + add;
+ *                         mean and biased variance per (b, c) over the T frames, `eps`, no affine; every `subsampling`-th
+ *                         frame (T_in = ceil(T / subsampling)); then F.interpolate(mode="linear", align_corners=False) to T_out
+ *                         frames: src = max(T_in / T_out * (j + 0.5) - 0.5, 0) in fp32, i0 = floor(src), i1 = min(i0 + 1,
+ *                         T_in - 1), out = (1 - f) x[i0] + f x[i1].  out[b, j, c] channel-last with a batch and a row stride
+ *                         (elements).  `states`, `stride_b`, `stride_t` are HOST arrays of n_states <= 32 device pointers /
+ *                         element strides (unit channel stride), `weights` fp32 [n_states] on the device (softmax applied).
+ *                         Every state element is read once for T <= 1536 (the mixed slab of 16 channels stays in LDS, 96 KiB);
+ *                         a later frame is mixed again once for the variance and once per interpolation tap that uses it (up
+ *                         to four reads of those frames when T_out <= T_in).
+ *   wavlm_attn_plain_fwd  transformer.py:55-69: O[b, t, h * d + :] = softmax_j(scale * q[b, t, h] . k[b, j, h]) v[b, j, h] from
+ *                         the packed qkv [B, T, 3 * H * d] (q | k | v, head h at h * d inside each), O [B, T, H * d], both of
+ *                         `dtype`, 16-byte aligned.  head_dim must be 32; any T; online softmax, no [B H, T, T] tensor.  bf16:
+ *                         both products on v_mfma_f32_32x32x16_bf16 with fp32 softmax state (P rounded to bf16 as the operand
+ *                         only); fp32: fp32 FMA throughout.  No bias, mask or dropout: the reference has none in eval.
+ *   wavlm_diar_estimate   models.py:232-250,325-344.  z [B, T, ldz] holds, per frame, S activity logits then S vectors of E
+ *                         (the output of one GEMM over `linear` | `linear0` .. concatenated; ldz >= S + S * E, E <= 512).
+ *                         activities fp32 [B, T, S] = sigmoid(logits); vectors [B, S, E] (v_dtype) = normalize(sum_t
+ *                         activities[b, t, s] * z[b, t, s, :] / |z[b, t, s, :]|): per-frame normalisation, weight, sum over
+ *                         time (inside one workgroup, fixed order), final normalisation -- estimate()'s order.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_diar_front(const void* const* states, const int64_t* stride_b, const int64_t* stride_t, int32_t n_states,
+                     int32_t dtype, const float* weights, int32_t B, int32_t T, int32_t D, int32_t subsampling, int32_t T_out,
+                     void* out, int32_t out_dtype, int64_t out_stride_b, int64_t out_stride_t, float add, float eps,
+                     void* stream);
+int wavlm_attn_plain_fwd(const void* qkv, void* O, int32_t B, int32_t H, int32_t T, int32_t head_dim, int32_t dtype,
+                         float scale, void* stream);
+int wavlm_diar_estimate(const void* z, int32_t z_dtype, int64_t z_stride_b, int64_t ldz, int32_t B, int32_t T, int32_t S,
+                        int32_t E, float* activities, void* vectors, int32_t v_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

@@ -884,3 +884,54 @@ def mix_utterances(src, ops_flat, n_ops, op_begin, noise, normalize, out_dtype=t
                                  ptr(op_begin), ptr(noise), int(bool(normalize)), float(eps), ptr(ws), need, stream()),
           "wavlm_mix_utterances")
     return low if low is not None else dst
+
+
+# ------------------------------------------------------------------------------------ diarization head (csrc/diar.hip)
+def diar_front(states, weights, T_out, subsampling=1, add=1e-6, eps=1e-5, out=None):
+    """states: L + 1 tensors [B, T', D] (unit channel stride), weights fp32 [L + 1] (softmax applied) -> [B, T_out, D]:
+    layer mix + add, InstanceNorm1d over time, every subsampling-th frame, linear interpolation to T_out frames"""
+    s0 = states[0]
+    dev = _dev(s0)
+    if s0.dim() != 3 or any(s.shape != s0.shape or s.dtype != s0.dtype or s.device != dev or s.stride(2) != 1
+                            or s.stride(1) < s.shape[2] for s in states):
+        raise ValueError("states must share one shape [B, T', D], dtype and device and have unit channel stride")
+    B, T, D = s0.shape
+    n = len(states)
+    if weights.numel() != n or weights.dtype != torch.float32 or weights.device != dev or not weights.is_contiguous():
+        raise ValueError("weights must be %d contiguous fp32 values on the states' device" % n)
+    if out is None:
+        out = torch.empty((B, T_out, D), dtype=s0.dtype, device=dev)
+    ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in states])
+    sb = (C.c_int64 * n)(*[s.stride(0) for s in states])
+    stt = (C.c_int64 * n)(*[s.stride(1) for s in states])
+    check(_lib.lib().wavlm_diar_front(ptrs, sb, stt, n, dt(s0), ptr(weights), B, T, D, int(subsampling), int(T_out), ptr(out),
+                                      dt(out), out.stride(0), out.stride(1), float(add), float(eps), stream()),
+          "wavlm_diar_front")
+    return out
+
+
+def attn_plain_fwd(qkv, H, scale=None):
+    """packed qkv [B, T, 3 * H * d] (d = 32) -> softmax(scale * Q K^T) V as [B, T, H * d]; scale defaults to 1 / sqrt(d)"""
+    _dev(qkv)
+    _contig(qkv)
+    B, T, D3 = qkv.shape
+    d = D3 // (3 * H)
+    if d * 3 * H != D3:
+        raise ValueError("qkv width %d is not 3 * %d heads * head_dim" % (D3, H))
+    O = torch.empty((B, T, H * d), dtype=qkv.dtype, device=qkv.device)
+    check(_lib.lib().wavlm_attn_plain_fwd(ptr(qkv), ptr(O), B, H, T, d, dt(qkv), float(scale if scale is not None else d ** -0.5),
+                                          stream()), "wavlm_attn_plain_fwd[B=%d H=%d T=%d d=%d]" % (B, H, T, d))
+    return O
+
+
+def diar_estimate(z, S, E):
+    """z [B, T, >= S + S * E] (logits | S vectors per frame) -> (activities fp32 [B, T, S], vectors [B, S, E])"""
+    dev = _dev(z)
+    B, T, ld = z.shape
+    if z.stride(2) != 1 or z.stride(1) < ld:
+        raise ValueError("expected unit channel stride")
+    act = torch.empty((B, T, S), dtype=torch.float32, device=dev)
+    vec = torch.empty((B, S, E), dtype=z.dtype, device=dev)
+    check(_lib.lib().wavlm_diar_estimate(ptr(z), dt(z), z.stride(0), z.stride(1), B, T, int(S), int(E), ptr(act), ptr(vec), dt(vec),
+                                         stream()), "wavlm_diar_estimate")
+    return act, vec

@@ -100,7 +100,56 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-class ECAPA_TDNN(nn.Module):
+class UpstreamStates:
+    """what every head over the upstream's layer states shares (this file's ECAPA_TDNN, diarization.TransformerDiarization):
+    the model sits at self.feature_extract.model"""
+
+    def _states_of(self, wav):
+        """wav [b, n] (equal lengths) -> list of L + 1 tensors [b, T', D] in the reference's hook order (utils.py:49-56):
+        the input of every encoder layer, then the encoder's output (after the final LayerNorm for a pre-LN stack)"""
+        m = self.feature_extract.model
+        x, _ = m._features(wav)
+        enc = m.encoder
+        L = len(enc.layers)
+        _, results, _ = enc.extract_features(x, None, tgt_layer=L - 1)
+        states = [r[0].transpose(0, 1) for r in results]   # [T, B, D] views of channel-last tensors: back to the tensors
+        assert len(states) == L + 1
+        if enc.layer_norm_first:
+            ln = enc.layer_norm
+            states[-1], _ = F.layer_norm(states[-1], ln.weight, ln.bias, ln.eps)
+        return states
+
+    def _wav_list(self, wavs):
+        if isinstance(wavs, torch.Tensor):
+            if wavs.dim() == 1:
+                wavs = wavs.unsqueeze(0)
+            if wavs.dim() != 2:
+                raise NotImplementedError("input of shape %s: 16 kHz mono waveforms [B, T] or a list of 1-D tensors are "
+                                          "expected" % (tuple(wavs.shape),))
+            return list(wavs.unbind(0))
+        wavs = [torch.as_tensor(w) for w in wavs]
+        for w in wavs:
+            if w.dim() != 1:
+                raise NotImplementedError("a waveform of shape %s: 16 kHz mono (1-D) is expected; the reference resamples "
+                                          "and down-mixes with torchaudio, which is not built" % (tuple(w.shape),))
+        return wavs
+
+    def _prepared_wavs(self, wavs):
+        """fp32 on the upstream's device, layer-normed when its cfg.normalize is set (UpstreamExpert.forward,
+        utils.py:59-60), then its dtype"""
+        m = self.feature_extract.model
+        p0 = next(m.parameters())
+        normalize = bool(getattr(m.cfg, "normalize", False))
+        prepared = []
+        for w in wavs:
+            w = w.to(device=p0.device, dtype=torch.float32)
+            if normalize:
+                w = torch.nn.functional.layer_norm(w, w.shape)
+            prepared.append(w.to(p0.dtype))
+        return prepared
+
+
+class ECAPA_TDNN(UpstreamStates, nn.Module):
     """ecapa_tdnn.py:163-286 with feat_type = an upstream model and feature_selection="hidden_states".
 
     feat_dim: width D of the states; upstream: a unispeech_amd.wavlm.WavLM (its keys appear under feature_extract.model.*)
@@ -209,37 +258,7 @@ class ECAPA_TDNN(nn.Module):
             raise NotImplementedError("forward with gradients required is not built (inference only): run under "
                                       "torch.no_grad()")
 
-    # -- upstream ------------------------------------------------------------------------------------------------------
-    def _states_of(self, wav):
-        """wav [b, n] (equal lengths) -> list of L + 1 tensors [b, T', D] in the reference's hook order (utils.py:49-56):
-        the input of every encoder layer, then the encoder's output (after the final LayerNorm for a pre-LN stack)"""
-        m = self.feature_extract.model
-        x, _ = m._features(wav)
-        enc = m.encoder
-        L = len(enc.layers)
-        _, results, _ = enc.extract_features(x, None, tgt_layer=L - 1)
-        states = [r[0].transpose(0, 1) for r in results]   # [T, B, D] views of channel-last tensors: back to the tensors
-        assert len(states) == L + 1
-        if enc.layer_norm_first:
-            ln = enc.layer_norm
-            states[-1], _ = F.layer_norm(states[-1], ln.weight, ln.bias, ln.eps)
-        return states
-
-    def _wav_list(self, wavs):
-        if isinstance(wavs, torch.Tensor):
-            if wavs.dim() == 1:
-                wavs = wavs.unsqueeze(0)
-            if wavs.dim() != 2:
-                raise NotImplementedError("input of shape %s: 16 kHz mono waveforms [B, T] or a list of 1-D tensors are "
-                                          "expected" % (tuple(wavs.shape),))
-            return list(wavs.unbind(0))
-        wavs = [torch.as_tensor(w) for w in wavs]
-        for w in wavs:
-            if w.dim() != 1:
-                raise NotImplementedError("a waveform of shape %s: 16 kHz mono (1-D) is expected; the reference resamples "
-                                          "and down-mixes with torchaudio, which is not built" % (tuple(w.shape),))
-        return wavs
-
+    # -- upstream: UpstreamStates ---------------------------------------------------------------------------------------
     def hidden_states(self, wavs):
         """list of 1-D waveforms or [B, T] -> (states: L + 1 tensors [B, T'max, D], lengths: frames per utterance, or None
         when all are equal).  The waveform is layer-normed first when the upstream's cfg.normalize is set
@@ -250,14 +269,7 @@ class ECAPA_TDNN(nn.Module):
             raise ValueError("this head was built without an upstream: use forward_states")
         m = self.feature_extract.model
         wavs = self._wav_list(wavs)
-        p0 = next(m.parameters())
-        normalize = bool(getattr(m.cfg, "normalize", False))
-        prepared = []
-        for w in wavs:
-            w = w.to(device=p0.device, dtype=torch.float32)
-            if normalize:
-                w = torch.nn.functional.layer_norm(w, w.shape)
-            prepared.append(w.to(p0.dtype))
+        prepared = self._prepared_wavs(wavs)
         groups = group_by_length(len(w) for w in prepared)
         with torch.no_grad():
             if len(groups) == 1:
