@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 24
+#define WAVLM_HIP_ABI_VERSION 25
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -313,20 +313,24 @@ int wavlm_l2norm_fwd(const void* x, int32_t x_dtype, void* y, int32_t y_dtype, f
 int wavlm_l2norm_bwd(const void* dy, const void* y, int32_t y_dtype, const float* inv_norm, void* dx, int32_t x_dtype,
                      int64_t rows, int32_t D, void* stream);
 /* per row: loss = logsumexp(logits) - logits[target]; correct = (logits[target] is the row max);
- * dlogits (optional) = weight * (softmax - onehot), zero-filled up to ld_dlogits */
+ * dlogits (optional) = weight * (softmax - onehot), zero-filled up to ld_dlogits.
+ * flat_wrong (ABI 25): a row whose V logits are all equal counts as not correct -- the wav2vec criterion's
+ * (argmax == 0) minus (argmax == 0 and argmin == 0), criterions/wav2vec_criterion.py:105-113, with the target in column 0. */
 int wavlm_ce_rows(const float* logits, const int32_t* target, float* loss_rows, float* correct_rows, void* dlogits,
                   int32_t d_dtype, int64_t S, int32_t V, int64_t ld_logits, int64_t ld_dlogits, float weight,
-                  void* stream);
+                  int32_t flat_wrong, void* stream);
 
 /* Sampled-instance cosine logits + BCE: the utterance-contrastive head of UniSpeech-SAT
  * (src/fairseq/models/unispeech_sat/unispeech_sat.py:487-557 sample_instances / compute_nce, 701-737 compute_pred_spk;
  * the same gathered-cosine shape as wav2vec 2.0's sample_negatives, models/wav2vec/wav2vec2.py:474-553).
  * X, Y: L2-normalised rows (X = Y for UniSpeech-SAT); idx[s, n]: row of Y gathered for logit n of row s (the host draws
- * the indices with the reference's torch.randint calls); out[s, n] = scale * <X[s], Y[idx[s, n]]>; mask_equal: logits
- * n >= 1 whose gathered row equals the row of column 0 become -inf (wav2vec 2.0's neg_is_pos, wav2vec2.py:535-551).  rows_wsum is both halves of its backward:
+ * the indices with the reference's torch.randint calls); out[s, n] = scale * <X[s], Y[idx[s, n]]>; mask_raw (ABI 25; NULL = no
+ * masking): the rows of Y before normalisation, same shape and dtype -- logits n >= 1 whose gathered row of mask_raw equals the
+ * row of column 0 become -inf (wav2vec 2.0's neg_is_pos, wav2vec2.py:535-551, which compares the un-normalised targets: a
+ * positive multiple of the positive is NOT masked).  rows_wsum is both halves of its backward:
  * out[j] (+)= sum_{e in [off[j], off[j+1])} w[e] * Y[src[e]]. */
 int wavlm_gather_dot(const void* X, const void* Y, int32_t dtype, const int32_t* idx, float* out, int64_t S, int32_t N,
-                     int32_t D, float scale, int32_t mask_equal, void* stream);
+                     int32_t D, float scale, const void* mask_raw, void* stream);
 int wavlm_rows_wsum(const void* Y, int32_t dtype, const int32_t* src, const float* w, const int32_t* off, void* out,
                     int32_t out_dtype, int64_t rows, int32_t D, int32_t accumulate, void* stream);
 uint64_t wavlm_bce_workspace_bytes(void);
@@ -376,15 +380,17 @@ int wavlm_mix_utterances(const float* src, float* dst, void* dst_lowp, int32_t B
  * wavlm_gather_rows with the returned indices).
  *   fwd: idx[n*G] = g*V + argmax (training: of (logits + gumbel)/tau, else of the raw logits); ysoft[n*G, V] =
  *        softmax((logits + gumbel)/tau) (training only); noise = the Gumbel draws [n*G, V] (fp32) or NULL for a device
- *        counter hash of `seed`; part[wavlm_gumbel_vq_partial_rows(n)][2*G*V] = per-wave column sums of softmax(raw
- *        logits) and of the hard one-hot (sum the rows with wavlm_colsum).
+ *        counter hash of `seed`; part[wavlm_gumbel_vq_partial_rows(n)][ld_part >= 2*G*V] = per-wave column sums of softmax(raw
+ *        logits) and of the hard one-hot (sum the rows with wavlm_colsum; ld_part, ABI 25, lets the caller round the row up
+ *        to wavlm_colsum's 8-column granule when G*V is not a multiple of 4 -- columns beyond 2*G*V are not written).
  *   perplexity: sums[2][G*V] -> out[0] = prob_perplexity, out[1] = code_perplexity, dA[G*V] = d prob_ppl / d avg_probs.
  *   bwd: dlogits = ysoft*(dret - <ysoft,dret>)/tau (if ysoft/dret given) + dppl[0] * softmax(raw)*(dA - <softmax,dA>)/n
  *        (if dppl given).  G <= 4, V <= 320.
  * ------------------------------------------------------------------------------------------ */
 uint64_t wavlm_gumbel_vq_partial_rows(int64_t n);
 int wavlm_gumbel_vq_fwd(const void* logits, int32_t dtype, const float* noise, uint64_t seed, float tau, int32_t training,
-                        int64_t n, int32_t G, int32_t V, float* ysoft, int32_t* idx, float* part, void* stream);
+                        int64_t n, int32_t G, int32_t V, float* ysoft, int32_t* idx, float* part, int64_t ld_part,
+                        void* stream);
 int wavlm_vq_perplexity(const float* sums, int64_t n, int32_t G, int32_t V, float* out, float* dA, void* stream);
 int wavlm_gumbel_vq_bwd(const void* logits, int32_t dtype, const float* ysoft, const float* dret, const float* dA,
                         const float* dppl, float tau, int64_t n, int32_t G, int32_t V, void* dlogits, void* stream);

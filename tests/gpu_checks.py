@@ -1054,6 +1054,504 @@ def check_loss():
     return out
 
 
+
+# ------------------------------------------------------------- wav2vec 2.0 / UniSpeech quantised-target head
+def argmax_lowest(t):
+    """arg-max over the last dimension with the tie rule spelled out: the LOWEST index among the maxima"""
+    V = t.shape[-1]
+    mx = t.max(-1, keepdim=True).values
+    ar = torch.arange(V).expand(t.shape)
+    return torch.where(t == mx, ar, torch.full_like(ar, V)).min(-1).values
+
+
+def prob_perplexity_of(avg_probs):
+    """sum over groups of exp(entropy) of avg_probs [G, V] (gumbel_vector_quantizer.py:184-190)"""
+    return torch.exp(-torch.sum(avg_probs * torch.log(avg_probs + 1e-7), dim=-1)).sum()
+
+
+def ref_gumbel_vq(logits, vars_, G, V, tau, training, noise):
+    """GumbelVectorQuantizer.forward (src/fairseq/modules/gumbel_vector_quantizer.py:157-213; oracle.gumbel_vq) after the
+    weight projection, line by line, in the dtype of its inputs (fp64 in the checks), with the Gumbel draws passed in:
+    logits [n, G*V], vars_ [1, G*V, vd], noise [n*G, V] or None (eval).  F.gumbel_softmax(hard=True) is written out as
+    y_hard - y_soft.detach() + y_soft, so autograd gives the reference's straight-through gradients.
+    Returns (x [n, G*vd], prob_perplexity, code_perplexity, idx [n, G] (code within its group), y_soft [n*G, V] or None)."""
+    n = logits.shape[0]
+    lg = logits.reshape(n * G, V)
+    k = argmax_lowest(lg)
+    hard_x = torch.zeros_like(lg).scatter_(-1, k.view(-1, 1), 1.0).view(n, G, V)
+    hard_probs = torch.mean(hard_x, dim=0)
+    code_ppl = torch.exp(-torch.sum(hard_probs * torch.log(hard_probs + 1e-7), dim=-1)).sum()
+    avg_probs = torch.softmax(lg.view(n, G, V), dim=-1).mean(dim=0)
+    prob_ppl = prob_perplexity_of(avg_probs)
+    y_soft = None
+    if training:
+        y_soft = torch.softmax((lg + noise) / tau, dim=-1)
+        k = argmax_lowest(y_soft)
+        y_hard = torch.zeros_like(lg).scatter_(-1, k.view(-1, 1), 1.0)
+        y = y_hard - y_soft.detach() + y_soft
+    else:
+        y = hard_x
+    y = y.reshape(n, -1)
+    x = (y.unsqueeze(-1) * vars_).view(n, G, V, -1).sum(-2).view(n, -1)
+    return x, prob_ppl, code_ppl, k.view(n, G), y_soft
+
+
+def ref_sampled_negatives(x, y, idx, temp):
+    """Wav2Vec2Model.compute_preds (models/wav2vec/wav2vec2.py:533-553) + Wav2vecCriterion with infonce
+    (criterions/wav2vec_criterion.py:44-64, 105-113): x [S, C], y [R, C], idx int64 [S, 1 + N] rows of y (column 0 = the
+    positive).  neg_is_pos compares the RAW rows of y.  Returns (loss summed, n_correct, logits [S, N + 1])."""
+    pos = y[idx[:, 0]]                                   # [S, C]
+    negs = y[idx[:, 1:]].permute(1, 0, 2)                # [N, S, C]
+    neg_is_pos = (pos == negs).all(-1)                   # [N, S]
+    targets = torch.cat([pos.unsqueeze(0), negs], dim=0)
+    logits = torch.cosine_similarity(x, targets, dim=-1) / temp
+    if neg_is_pos.any():
+        logits = torch.cat([logits[:1], logits[1:].masked_fill(neg_is_pos, float("-inf"))], dim=0)
+    l2 = logits.transpose(0, 1)                          # [S, N + 1]
+    loss = TF.cross_entropy(l2, torch.zeros(l2.size(0), dtype=torch.long), reduction="sum")
+    mx, mn = l2.argmax(-1) == 0, l2.argmin(-1) == 0
+    n_correct = int(mx.long().sum().item() - (mx & mn).long().sum().item())
+    return loss, n_correct, l2
+
+
+def chi2_quantile(df, tail=1e-6):
+    """the chi-square(df) quantile at 1 - tail: scipy when importable, else the Wilson-Hilferty cube"""
+    try:
+        from scipy.stats import chi2
+        return float(chi2.isf(tail, df))
+    except ImportError:
+        from statistics import NormalDist
+        z = NormalDist().inv_cdf(1.0 - tail)
+        return df * (1.0 - 2.0 / (9.0 * df) + z * math.sqrt(2.0 / (9.0 * df))) ** 3
+
+
+def chi2_independence(a, b, K):
+    """Pearson statistic of the K x K contingency table of two index vectors against the product of its margins"""
+    tab = torch.bincount(a.long() * K + b.long(), minlength=K * K).double().view(K, K)
+    exp = tab.sum(1, keepdim=True) * tab.sum(0, keepdim=True) / tab.sum()
+    return float(((tab - exp) ** 2 / exp).sum().item())
+
+
+def seeded_gumbel(rows, V, seed):
+    """F.gumbel_softmax's draws (-log of Exp(1) samples), from a generator of their own"""
+    g = torch.Generator().manual_seed(seed)
+    return -torch.empty((rows, V), dtype=torch.float32).exponential_(generator=g).log()
+
+
+def vq_near_ties(lg64, noise64, tau):
+    """rows [n*G] whose top-two gap of z = (l + g) / tau in fp64 is below 8 * 2^-23 * max|z| of the row: the fp32 rounding
+    of the kernel's (l + g) * inv_tau can order those two either way"""
+    z = (lg64 + noise64) / tau
+    if z.shape[-1] < 2:
+        return torch.zeros(z.shape[0], dtype=torch.bool)
+    top = z.topk(2, dim=-1).values
+    return (top[:, 0] - top[:, 1]) < 8.0 * 2.0 ** -23 * z.abs().max(-1).values
+
+
+# (G, V, n, seed).  The seeds are ones for which the fp64 reference alone has NO near-tie row (vq_near_ties) in either dtype,
+# so that x and dvars, which follow the chosen index, can be compared on every row.
+VQ_CASES = [(1, 1, 37, 100), (2, 20, 45, 110), (1, 64, 101, 120), (2, 65, 77, 130), (3, 100, 53, 140), (4, 129, 66, 150),
+            (2, 319, 83, 160), (2, 320, 301, 170), (2, 320, 8192 + 37, 180), (4, 320, 4099, 198)]
+VQ_TAU = 0.7          # between the schedule's ends (2.0 -> 0.5)
+VQ_DIV_WEIGHT = 0.1   # loss_weights[0] of the released wav2vec 2.0 recipes
+
+
+def vq_case_inputs(G, V, n, dtype, seed):
+    """(logits [n, G*V] at scale 3, codebook [1, G*V, vd], Gumbel noise [n*G, V], dx weights [n, G*vd]), rounded through
+    dtype where the device holds them in dtype; vd is a multiple of 8 (the GEMM's tested K granule)"""
+    vd = 8 if n > 1000 else 16
+    return (q(gen(n, G * V, seed=seed, scale=3.0), dtype), q(gen(1, G * V, vd, seed=seed + 1), dtype),
+            seeded_gumbel(n * G, V, seed + 2), q(gen(n, G * vd, seed=seed + 3), dtype))
+
+
+def vq_tie_inputs(dtype, training):
+    """rows of a G = 2, V = 320 problem whose maximum appears twice, bit-equal: per row (code a, code b, lowest).  Eval: both
+    logits are 9 (exact in bf16).  Training: logits 20 and 21 with noise 1.5 and 0.5, so the SUMS are both 21.5 (exact in
+    fp32) while the raw arg-max is the higher code; every other sum stays far below (|l| < 6, Gumbel < 16 never reached)."""
+    G, V = 2, 320
+    pairs = [(3, 40), (5, 70), (63, 64), (0, V - 1), (130, 131), (191, 192), (64, 256), (17, 273), (255, 256), (127, 128)]
+    n = len(pairs)
+    logits = q(gen(n, G * V, seed=77, scale=1.0), dtype).view(n, G, V)
+    noise = seeded_gumbel(n * G, V, 78).view(n, G, V)
+    want = torch.zeros(n, G, dtype=torch.long)
+    for r, (lo, hi) in enumerate(pairs):
+        for g in range(G):
+            if training:   # group 0: the higher raw logit at the higher code; group 1: at the lower code
+                big, small = (hi, lo) if g == 0 else (lo, hi)
+                logits[r, g, big], noise[r, g, big] = 21.0, 0.5
+                logits[r, g, small], noise[r, g, small] = 20.0, 1.5
+            else:
+                logits[r, g, lo] = logits[r, g, hi] = 9.0
+            want[r, g] = lo
+    return G, V, logits.reshape(n, G * V).contiguous(), noise.reshape(n * G, V).contiguous(), want
+
+
+def check_gumbel_vq():
+    """csrc/vq.hip + functional.GumbelVQFn against ref_gumbel_vq in fp64 at the released codebook size (V = 320: all five
+    lane chunks), every group count, ragged V, row counts beyond one grid pass, both dtypes; the device Gumbel generator's
+    law, independence and moments; the API limits.  Tested envelope: V <= 320, G <= 4."""
+    from unispeech_amd import _lib
+    out = []
+    for dtype in (torch.float32, torch.bfloat16):
+        tol = tol_for(dtype)
+        dn = "fp32" if dtype == torch.float32 else "bf16"
+        for (G, V, n, seed) in VQ_CASES:
+            tag = f"gumbel_vq[{dn}] G={G} V={V} n={n}"
+            logits, vars_, noise, dxw = vq_case_inputs(G, V, n, dtype, seed)
+            vd = vars_.shape[-1]
+            ld, vdev = logits.to(dtype).to(DEV), vars_.to(dtype).to(DEV)
+            goff = torch.arange(G) * V
+            div_w = -VQ_DIV_WEIGHT * n / (G * V)     # d criterion / d prob_perplexity: 0.1 * sample_size * (GV - ppl) / GV
+            # ---- eval mode: the arg-max does no arithmetic -> exact
+            l64 = logits.double().requires_grad_(True)
+            v64 = vars_.double().requires_grad_(True)
+            xr, pr, cr, kr, _ = ref_gumbel_vq(l64, v64, G, V, VQ_TAU, False, None)
+            idx, _, ppl, dA = ops.gumbel_vq_fwd(ld, G, V, VQ_TAU, False)
+            kd = idx.cpu().long().view(n, G) - goff
+            out.append((tag + " eval idx (mismatches)", float((kd != kr).sum().item()), 0.0))
+            le = ld.clone().requires_grad_(True)
+            xd, pd, cd = F.GumbelVQFn.apply(le, vdev, G, V, VQ_TAU, False, None, 0)
+            pick = vdev.view(G * V, vd)[(kr + goff).view(-1)].view(n, G * vd)
+            out.append((tag + " eval x == vars[idx] (differing elements)", float((xd != pick).sum().item()), 0.0))
+            out.append((tag + " eval prob_perplexity", err(pd, pr.reshape(1)), tol))
+            out.append((tag + " eval code_perplexity", err(cd, cr.reshape(1)), tol))
+            out.append((tag + " perplexity pair of the forward call", err(ppl, torch.stack([pr, cr])), tol))
+            avg = torch.softmax(logits.double().view(n, G, V), -1).mean(0).requires_grad_(True)
+            (dAr,) = torch.autograd.grad(prob_perplexity_of(avg), avg)
+            out.append((tag + " dA = d prob_perplexity / d avg_probs", err(dA, dAr.reshape(-1)), tol))
+            # backward 2: eval mode, the diversity term alone, at its own scale
+            (dl_ref,) = torch.autograd.grad(pr * div_w, l64)
+            (dl_dev,) = torch.autograd.grad(pd.sum() * div_w, le)
+            out.append((tag + " bwd diversity term alone: dlogits", err(dl_dev, dl_ref), tol * 3))
+            # ---- training with host noise
+            l64 = logits.double().requires_grad_(True)
+            xr, pr, cr, kr, yr = ref_gumbel_vq(l64, v64, G, V, VQ_TAU, True, noise.double())
+            nd = noise.to(DEV)
+            idx, ys, ppl, dA = ops.gumbel_vq_fwd(ld, G, V, VQ_TAU, True, nd)
+            kd = idx.cpu().long().view(n, G) - goff
+            near = vq_near_ties(logits.double().view(n * G, V), noise.double(), VQ_TAU)
+            nex = int(near.sum().item())
+            out.append((tag + " train y_soft", err(ys, yr), TOL32))
+            out.append((tag + f" train idx (mismatches outside the {nex} near-tie rows of {n * G})",
+                        float(((kd != kr).view(-1) & ~near).sum().item()), 0.0))
+            out.append((tag + f" train near-tie rows excluded: {nex} of {n * G} (cap 0.1 %)", nex / (n * G), 1e-3))
+            out.append((tag + " train perplexity pair", err(ppl, torch.stack([pr, cr]).detach()), tol))
+            # backward 1: the straight-through term alone; backward 3: both, weighted as the criterion does
+            lt = ld.clone().requires_grad_(True)
+            vt = vdev.clone().requires_grad_(True)
+            xd, pd, _ = F.GumbelVQFn.apply(lt, vt, G, V, VQ_TAU, True, nd, 0)
+            out.append((tag + " train x", err(xd, xr), tol))
+            dxd = dxw.to(dtype).to(DEV)
+            g1 = torch.autograd.grad(xd, (lt, vt), dxd, retain_graph=True)
+            r1 = torch.autograd.grad((xr * dxw.double()).sum(), (l64, v64), retain_graph=True)
+            out.append((tag + " bwd straight-through term alone: dlogits", err(g1[0], r1[0]), tol * 3))
+            out.append((tag + " bwd straight-through term alone: dvars", err(g1[1], r1[1]), tol * 3))
+            g3 = torch.autograd.grad((xd.float() * dxd.float()).sum() + pd.sum() * div_w, (lt, vt))
+            r3 = torch.autograd.grad((xr * dxw.double()).sum() + pr * div_w, (l64, v64))
+            out.append((tag + " bwd both terms: dlogits", err(g3[0], r3[0]), tol * 3))
+            out.append((tag + " bwd both terms: dvars", err(g3[1], r3[1]), tol * 3))
+        # ---- tie rule: the maximum twice, bit-equal -> the lowest index, exactly
+        for training in (False, True):
+            G, V, logits, noise, want = vq_tie_inputs(dtype, training)
+            n = logits.shape[0]
+            idx, _, _, _ = ops.gumbel_vq_fwd(logits.to(dtype).to(DEV), G, V, VQ_TAU, training, noise.to(DEV) if training else None)
+            kd = idx.cpu().long().view(n, G) - torch.arange(G) * V
+            _, _, _, kr, _ = ref_gumbel_vq(logits.double(), torch.zeros(1, G * V, 1).double(), G, V, VQ_TAU, training,
+                                           noise.double() if training else None)
+            md = "equal logit + noise sums (training)" if training else "equal logits (eval)"
+            out.append((f"gumbel_vq[{dn}] ties, {md}: rows not at the lowest index", float((kd != want).sum().item()), 0.0))
+            out.append((f"gumbel_vq[{dn}] ties, {md}: reference not at the lowest index", float((kr != want).sum().item()), 0.0))
+        # ---- perplexities / dA at the edges: codes with softmax mass ~ 0 that are never chosen (the a -> 0 branch of
+        # log(a + 1e-7)), one code taking every row (perplexity ~ 1 per group), one code taken by most rows in training
+        G, V, n = 2, 320, 50
+        for kind in ("unused block", "one code", "dominant code"):
+            logits = gen(n, G, V, seed=301, scale=3.0)
+            if kind == "unused block":
+                logits[:, :, 100:200] = -30.0
+            elif kind == "one code":
+                logits[:, 0, 7] = 40.0
+                logits[:, 1, 300] = 40.0
+            else:
+                logits[:, 0, 7] += 12.0
+                logits[:, 1, 300] += 12.0
+            logits = q(logits.reshape(n, G * V), dtype)
+            vars_ = q(gen(1, G * V, 16, seed=302), dtype)
+            noise = seeded_gumbel(n * G, V, 303)
+            training = kind == "dominant code"
+            l64 = logits.double().requires_grad_(True)
+            v64 = vars_.double().requires_grad_(True)
+            xr, pr, cr, kr, _ = ref_gumbel_vq(l64, v64, G, V, VQ_TAU, training, noise.double() if training else None)
+            lt = logits.to(dtype).to(DEV).requires_grad_(True)
+            vt = vars_.to(dtype).to(DEV).requires_grad_(True)
+            nd = noise.to(DEV) if training else None
+            idx, _, ppl, dA = ops.gumbel_vq_fwd(lt.detach(), G, V, VQ_TAU, training, nd)
+            xd, pd, cd = F.GumbelVQFn.apply(lt, vt, G, V, VQ_TAU, training, nd, 0)
+            avg = torch.softmax(logits.double().view(n, G, V), -1).mean(0).requires_grad_(True)
+            (dAr,) = torch.autograd.grad(prob_perplexity_of(avg), avg)
+            tag = f"gumbel_vq[{dn}] {kind}"
+            cnt = torch.bincount((kr + torch.arange(G) * V).view(-1), minlength=G * V)
+            tag += f" (codes never chosen: {int((cnt == 0).sum())}, most chosen: {int(cnt.max())} of {n} rows)"
+            out.append((tag + " idx (mismatches)", float((idx.cpu().long().view(n, G) - torch.arange(G) * V != kr).sum().item()), 0.0))
+            out.append((tag + " prob_perplexity", err(pd, pr.reshape(1)), tol))
+            out.append((tag + " code_perplexity", err(cd, cr.reshape(1)), tol))
+            out.append((tag + " dA", err(dA, dAr.reshape(-1)), tol))
+            dxw = q(gen(n, G * 16, seed=304), dtype)
+            div_w = -VQ_DIV_WEIGHT * n / (G * V)
+            gd = torch.autograd.grad((xd.float() * dxw.to(DEV)).sum() + pd.sum() * div_w, (lt, vt))
+            gr = torch.autograd.grad((xr * dxw.double()).sum() + pr * div_w, (l64, v64))
+            if kind == "one code":
+                # eval mode: dlogits is the diversity term alone, gp p_v (dA_v - <p, dA>) with gp = div_w / n.  With p a one-hot
+                # to ~1e-17 the bracket cancels to ~1e-13 of |dA|, so any fp32 evaluation (the reference's own fp32 autograd
+                # has the same form) carries an absolute error of a few 2^-24 |gp| max|dA| and the tensor's own scale means
+                # nothing: the error is taken relative to the terms that cancel, |gp| max|dA|
+                scale = abs(div_w) / n * dAr.abs().max().item()
+                out.append((tag + " dlogits (relative to |gp| max|dA|, the terms that cancel)",
+                            (gd[0].double().cpu() - gr[0]).abs().max().item() / scale, tol * 3))
+            else:
+                out.append((tag + " dlogits", err(gd[0], gr[0]), tol * 3))
+            out.append((tag + " dvars", err(gd[1], gr[1]), tol * 3))
+    out += check_gumbel_vq_device_noise()
+    # ---- API limits: refused by the entry point (WL_EINVAL through check()), nothing launched
+    for nm, (G, V, tau) in (("V = 321", (1, 321, 1.0)), ("G = 5", (5, 8, 1.0)), ("tau = 0", (2, 20, 0.0))):
+        lg = torch.zeros(4, G * V, device=DEV)
+        for which in ("fwd", "bwd"):
+            try:
+                if which == "fwd":
+                    ops.gumbel_vq_fwd(lg, G, V, tau, True, None, 1)
+                else:
+                    ops.gumbel_vq_bwd(lg, None, None, torch.zeros(G * V, device=DEV), torch.ones(1, device=DEV), G, V, tau)
+                refused = False
+            except _lib.WavlmHipError:
+                refused = True
+            out.append((f"gumbel_vq {which} refuses {nm}", 0.0 if refused else 1.0, 0.0))
+    return out
+
+
+def check_gumbel_vq_device_noise():
+    """vq_gumbel (counter hash -> -log(-log u)), the generator training uses by default: reproducible per seed; by the
+    Gumbel-max identity P(idx = k) = softmax(l)_k (chi-square against n softmax(l)); independent across consecutive rows and
+    across groups (chi-square on 8 x 8 contingency tables); variance and skewness of a Gumbel.  Every threshold is the
+    chi-square quantile at 1 - 1e-6 or six standard errors: a correct generator fails one of them about once in 10^5
+    seeds, an aliased counter by orders of magnitude."""
+    out = []
+    G, V, n = 2, 320, 1000
+    lg = gen(n, G * V, seed=401, scale=3.0).to(DEV)
+    i1, y1, _, _ = ops.gumbel_vq_fwd(lg, G, V, 1.0, True, None, 12345)
+    i2, y2, _, _ = ops.gumbel_vq_fwd(lg, G, V, 1.0, True, None, 12345)
+    i3, _, _, _ = ops.gumbel_vq_fwd(lg, G, V, 1.0, True, None, 12346)
+    out.append(("gumbel_vq device noise: same seed, differing idx", float((i1 != i2).sum().item()), 0.0))
+    out.append(("gumbel_vq device noise: same seed, differing y_soft elements", float((y1 != y2).sum().item()), 0.0))
+    out.append(("gumbel_vq device noise: other seed, fraction of idx unchanged (< 1/2)", (i1 == i3).float().mean().item(), 0.5))
+    # law
+    G, V, n = 2, 40, 200000
+    perm = torch.randperm(G * V, generator=torch.Generator().manual_seed(402)).view(G, V)
+    ell = (2.5 * perm.double() / (G * V - 1)).float()           # fixed, non-uniform, range 2.5: min expected count > 1000
+    idx, _, _, _ = ops.gumbel_vq_fwd(ell.view(1, G * V).expand(n, G * V).contiguous().to(DEV), G, V, 1.0, True, None, 20240611)
+    k = idx.cpu().long().view(n, G) - torch.arange(G) * V
+    thr = chi2_quantile(V - 1)
+    for g in range(G):
+        expc = n * torch.softmax(ell[g].double(), -1)
+        cnt = torch.bincount(k[:, g].clamp(0, V - 1), minlength=V).double()
+        out.append((f"gumbel_vq device noise: law, group {g}: chi2({V - 1}) of counts vs n softmax(l) (min expected {expc.min():.0f})",
+                    float(((cnt - expc) ** 2 / expc).sum().item()), thr))
+    # independence
+    G, V = 2, 8
+    ell = (1.0 * torch.arange(G * V).double() / (G * V - 1)).float()
+    idx, _, _, _ = ops.gumbel_vq_fwd(ell.view(1, G * V).expand(n, G * V).contiguous().to(DEV), G, V, 1.0, True, None, 977)
+    k = (idx.cpu().long().view(n, G) - torch.arange(G) * V).clamp(0, V - 1)
+    thr = chi2_quantile((V - 1) * (V - 1))
+    for g in range(G):
+        for par in (0, 1):   # disjoint pairs (row, row + 1) starting at even / odd rows: independent samples of the pair
+            a, b = k[par:n - 1:2, g], k[par + 1:n:2, g]
+            m = min(a.numel(), b.numel())
+            out.append((f"gumbel_vq device noise: independence of rows r, r+1 (group {g}, r = {par} mod 2): chi2(49)",
+                        chi2_independence(a[:m], b[:m], V), thr))
+    out.append(("gumbel_vq device noise: independence of groups 0, 1 of a row: chi2(49)", chi2_independence(k[:, 0], k[:, 1], V), thr))
+    # moments: zero logits, tau = 1 -> log y_soft - row mean = the noise centred within its row
+    G, V, n = 2, 320, 2000
+    _, ys, _, _ = ops.gumbel_vq_fwd(torch.zeros(n, G * V, device=DEV), G, V, 1.0, True, None, 31337)
+    c = ys.double().cpu().log()
+    c = c - c.mean(-1, keepdim=True)
+    N = c.numel()
+    var = float((c ** 2).sum(-1).div(V - 1).mean().item())                       # unbiased under row centring
+    m3 = float((c ** 3).mean().item()) / ((1 - 1 / V) * (1 - 2 / V))              # E c^3 = kappa3 (1 - 1/V)(1 - 2/V)
+    skew = m3 / var ** 1.5
+    # Gumbel cumulants kappa_r = (r - 1)! zeta(r) -> central moments; standard errors of the sample variance and of the
+    # sample skewness m3 / m2^1.5 (delta method, influence function a (x^3 - mu3 - 3 mu2 x) - b (x^2 - mu2)) at N samples
+    z2, z3, z4, z5, z6 = math.pi ** 2 / 6, 1.2020569031595942, math.pi ** 4 / 90, 1.0369277551433699, math.pi ** 6 / 945
+    k2, k3, k4, k5, k6 = z2, 2 * z3, 6 * z4, 24 * z5, 120 * z6
+    mu2, mu3, mu4, mu5 = k2, k3, k4 + 3 * k2 ** 2, k5 + 10 * k3 * k2
+    mu6 = k6 + 15 * k4 * k2 + 10 * k3 ** 2 + 15 * k2 ** 3
+    se_var = math.sqrt((mu4 - mu2 ** 2) / N)
+    a, b = mu2 ** -1.5, 1.5 * mu3 * mu2 ** -2.5
+    se_skew = math.sqrt((a * a * (mu6 - mu3 ** 2 + 9 * mu2 ** 3 - 6 * mu2 * mu4) - 2 * a * b * (mu5 - 4 * mu2 * mu3)
+                         + b * b * (mu4 - mu2 ** 2)) / N)
+    out.append((f"gumbel_vq device noise: variance vs pi^2/6 = {mu2:.4f} (margin 6 x {se_var:.2e}, N = {N})", abs(var - mu2), 6 * se_var))
+    out.append((f"gumbel_vq device noise: skewness vs {mu3 / mu2 ** 1.5:.4f} (margin 6 x {se_skew:.2e}, N = {N})",
+                abs(skew - mu3 / mu2 ** 1.5), 6 * se_skew))
+    return out
+
+
+def sn_near_ties(l2):
+    """rows whose fp64 gap between logit 0 and the best other logit is below 8 * 2^-23 * max|logit| (finite entries)"""
+    fin = torch.where(torch.isfinite(l2), l2, torch.zeros_like(l2))
+    if l2.shape[1] < 2:
+        return torch.zeros(l2.shape[0], dtype=torch.bool)
+    return (l2[:, 0] - l2[:, 1:].max(-1).values).abs() < 8.0 * 2.0 ** -23 * fin.abs().max(-1).values
+
+
+def sn_compare(tag, x, y, idx, dtype, out, temp=0.1, skip_rows_x=None, skip_rows_y=None):
+    """one SampledNegativesLossFn case against ref_sampled_negatives in fp64: loss, logits (+ exact -inf placement) through a
+    direct gather_dot call, dx, dy, n_correct.  skip_rows_*: rows compared on their own (their 1 / eps gradients would
+    otherwise set the scale of the whole tensor).  Returns (device logits, reference logits, dx, dy)."""
+    tol = tol_for(dtype)
+    S = x.shape[0]
+    x64, y64 = x.double().requires_grad_(True), y.double().requires_grad_(True)
+    lr, ncr, l2 = ref_sampled_negatives(x64, y64, idx, temp)
+    gx, gy = torch.autograd.grad(lr, (x64, y64))
+    xd, yd = x.to(dtype).to(DEV).requires_grad_(True), y.to(dtype).to(DEV).requires_grad_(True)
+    idd = idx.to(torch.int32).to(DEV)
+    loss, nc = F.SampledNegativesLossFn.apply(xd, yd, idd, temp)
+    dx, dy = torch.autograd.grad(loss.sum(), (xd, yd))
+    xn, _ = ops.l2norm_fwd(xd.detach(), dtype)
+    yn, _ = ops.l2norm_fwd(yd.detach(), dtype)
+    lg = ops.gather_dot(xn, yn, idd, 1.0 / temp, mask_raw=yd.detach()).cpu()
+    mref, mdev = torch.isinf(l2) & (l2 < 0), torch.isinf(lg) & (lg < 0)
+    zero = torch.zeros(())
+    out.append((tag + " loss", err(loss, lr.reshape(1)), tol))
+    out.append((tag + f" -inf placement ({int(mref.sum())} masked in the reference; differing positions)", float((mref != mdev).sum().item()), 0.0))
+    out.append((tag + " logits", err(torch.where(mdev, zero, lg), torch.where(mref, zero.double(), l2.detach())), tol))
+    kx = torch.ones(S, dtype=torch.bool) if skip_rows_x is None else ~skip_rows_x
+    ky = torch.ones(y.shape[0], dtype=torch.bool) if skip_rows_y is None else ~skip_rows_y
+    out.append((tag + " dx", err(dx.cpu()[kx], gx[kx]), tol * 3))
+    out.append((tag + f" dy ({dy.shape[0]} rows)", err(dy.cpu()[ky], gy[ky]), tol * 3))
+    if skip_rows_x is not None:
+        out.append((tag + " dx, the skipped rows", err(dx.cpu()[~kx], gx[~kx]), tol * 3))
+    if skip_rows_y is not None:
+        out.append((tag + " dy, the skipped rows", err(dy.cpu()[~ky], gy[~ky]), tol * 3))
+    diff = abs(int(round(nc.item())) - ncr)
+    if dtype == torch.float32:
+        k = int(sn_near_ties(l2.detach()).sum().item())
+        out.append((tag + f" n_correct (beyond the {k} near-tie rows)", float(max(0, diff - k)), 0.0))
+        out.append((tag + f" near-tie rows: {k} of {S} (cap 0.1 %)", k / S, 1e-3))
+    else:
+        out.append((tag + " n_correct", float(diff), max(2.0, 0.02 * S)))
+    return lg, l2.detach(), dx.cpu(), dy.cpu()
+
+
+def check_sampled_negatives():
+    """functional.SampledNegativesLossFn (l2norm, gather_dot with the neg_is_pos mask, ce_rows, sum_f32, rows_wsum twice,
+    l2norm backward) against ref_sampled_negatives in fp64 at the released sizes (final_dim 256 / 768, 100 negatives), every
+    float4 lane chunk of gather_dot / rows_wsum (D = 260: first group of chunk 1; D = 1024: the limit), and the index
+    patterns of training.  Tested envelope: D <= 1024, D a multiple of 4."""
+    out = []
+    for dtype in (torch.float32, torch.bfloat16):
+        dn = "fp32" if dtype == torch.float32 else "bf16"
+        for ci, (S, N, D) in enumerate([(57, 10, 32), (1201, 100, 256), (700, 100, 768), (333, 13, 260), (130, 100, 1024), (5, 1, 4)]):
+            x, y = q(gen(S, D, seed=500 + ci), dtype), q(gen(S, D, seed=520 + ci), dtype)
+            neg = torch.randint(0, S, (S, N), generator=torch.Generator().manual_seed(540 + ci))
+            idx = torch.cat([torch.arange(S).view(S, 1), neg], dim=1)
+            sn_compare(f"sampled_negatives[{dn}] S={S} N={N} D={D}", x, y, idx, dtype, out)
+        # the index draws of training: sample_negatives_indices, without and with cross-utterance negatives
+        for (bsz, tsz, nn_, cross) in [(4, 150, 100, 0), (3, 200, 100, 10)]:
+            S, D = bsz * tsz, 256
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(560 + cross)
+                neg = F.sample_negatives_indices(bsz, tsz, tsz, nn_, cross).view(bsz, tsz, nn_ + cross).reshape(S, nn_ + cross)
+            idx = torch.cat([torch.arange(S).view(S, 1), neg], dim=1)
+            x, y = q(gen(S, D, seed=561), dtype), q(gen(S, D, seed=562), dtype)
+            sn_compare(f"sampled_negatives[{dn}] production draws bsz={bsz} tsz={tsz} N={nn_}+{cross}", x, y, idx, dtype, out)
+        # quantised targets repeat: y rows from a 12-entry codebook -> the negative IS the positive in ~ 1/12 of the entries
+        S, N, D = 400, 100, 256
+        cb = q(gen(12, D, seed=570), dtype)
+        y = cb[torch.randint(0, 12, (S,), generator=torch.Generator().manual_seed(571))]
+        x = q(gen(S, D, seed=572), dtype)
+        idx = torch.cat([torch.arange(S).view(S, 1), torch.randint(0, S, (S, N), generator=torch.Generator().manual_seed(573))], dim=1)
+        tag = f"sampled_negatives[{dn}] quantised-target repeats"
+        lg, l2, _, _ = sn_compare(tag, x, y, idx, dtype, out)
+        frac = torch.isinf(l2[:, 1:]).double().mean().item()
+        out.append((tag + f" masked fraction {frac:.3f} within [0.02, 0.20]", 0.0 if 0.02 <= frac <= 0.20 else 1.0, 0.0))
+        tgt0 = torch.zeros(S, dtype=torch.int32, device=DEV)
+        dlog = torch.full((S, N + 1), float("nan"), device=DEV)
+        ops.ce_rows(lg.to(DEV), tgt0, N + 1, N + 1, dlog, N + 1, 1.0, flat_wrong=True)
+        out.append((tag + " d loss / d logit at the masked entries (non-zero count)", float((dlog.cpu()[torch.isinf(l2)] != 0).sum().item()), 0.0))
+        # skewed gathers: one row of y gathered > 500 times, > 30 % of its rows never (positives in the first S rows only)
+        S, R, N, D = 300, 600, 20, 256
+        x, y = q(gen(S, D, seed=580), dtype), q(gen(R, D, seed=581), dtype)
+        gi = torch.Generator().manual_seed(582)
+        neg = torch.randint(0, 350, (S, N), generator=gi)
+        neg[torch.rand(S, N, generator=gi) < 0.3] = 7
+        idx = torch.cat([torch.arange(S).view(S, 1), neg], dim=1)
+        cnt = torch.bincount(idx.view(-1), minlength=R)
+        tag = f"sampled_negatives[{dn}] skewed gathers (row 7: {int(cnt[7])} times; never gathered: {int((cnt == 0).sum())} of {R} rows)"
+        _, _, _, dy = sn_compare(tag, x, y, idx, dtype, out)
+        out.append((tag + " premise: > 500 gathers of one row and >= 30 % of the rows never", 0.0 if cnt[7] > 500 and (cnt == 0).sum() >= 0.3 * R else 1.0, 0.0))
+        out.append((tag + " dy on the rows never gathered (non-zero elements)", float((dy[cnt == 0] != 0).sum().item()), 0.0))
+        # y with more rows than x (negatives_from_everywhere / codebook negatives): the positive points into y
+        S, N, D = 150, 30, 64
+        R = S + 200
+        x, y = q(gen(S, D, seed=590), dtype), q(gen(R, D, seed=591), dtype)
+        gi = torch.Generator().manual_seed(592)
+        idx = torch.cat([torch.randperm(R, generator=gi)[:S].view(S, 1), torch.randint(0, R, (S, N), generator=gi)], dim=1)
+        tag = f"sampled_negatives[{dn}] y has R = S + 200 = {R} rows"
+        _, _, _, dy = sn_compare(tag, x, y, idx, dtype, out)
+        out.append((tag + " dy row count", float(abs(dy.shape[0] - R)), 0.0))
+        # zero rows: the max(||.||, eps) clamp; the zero row of x has all logits equal (0): arg-max = arg-min = 0, which
+        # the criterion counts as NOT correct
+        S, N, D = 64, 10, 32
+        x, y = q(gen(S, D, seed=600), dtype), q(gen(S, D, seed=601), dtype)
+        x[3] = 0.0
+        y[5] = 0.0
+        idx = torch.cat([torch.arange(S).view(S, 1), torch.randint(0, S, (S, N), generator=torch.Generator().manual_seed(602))], dim=1)
+        idx[9, 2] = 5
+        tag = f"sampled_negatives[{dn}] zero rows"
+        rx, ry = torch.arange(S) == 3, torch.arange(S) == 5
+        lg, l2, dx, dy = sn_compare(tag, x, y, idx, dtype, out, skip_rows_x=rx, skip_rows_y=ry)
+        out.append((tag + " finite loss gradients", 0.0 if torch.isfinite(dx).all() and torch.isfinite(dy).all() else 1.0, 0.0))
+        _, corr = ops.ce_rows(lg.to(DEV), torch.zeros(S, dtype=torch.int32, device=DEV), N + 1, N + 1, None, 0, 1.0, flat_wrong=True)
+        ref_row = float((l2[3].argmax() == 0) and not (l2[3].argmin() == 0))
+        out.append((tag + f" all-equal logit row: kernel counts it as correct = {corr[3].item():.0f}, the criterion {ref_row:.0f}",
+                    abs(corr[3].item() - ref_row), 0.0))
+        # a negative that is a positive multiple of the positive: the raw rows differ, the reference does not mask it (its
+        # logit equals the positive's); the normalised rows the kernel multiplies are identical
+        S, N, D = 64, 10, 256
+        x, y = q(gen(S, D, seed=610), dtype), q(gen(S, D, seed=611), dtype)
+        y[40] = 2.0 * y[11]
+        idx = torch.cat([torch.arange(S).view(S, 1), torch.randint(0, S, (S, N), generator=torch.Generator().manual_seed(612))], dim=1)
+        idx[11, 4] = 40
+        idx[11, 6] = 11      # and the positive's own row among the negatives: masked
+        tag = f"sampled_negatives[{dn}] scaled duplicate y[j] = 2 y[pos]"
+        lg, l2, _, _ = sn_compare(tag, x, y, idx, dtype, out)
+        kv = lg[11, 4].item()
+        out.append((tag + f": reference logit {l2[11, 4].item():.4f} (not masked), kernel {kv:.4f}, positive {lg[11, 0].item():.4f}",
+                    0.0 if math.isfinite(kv) and kv == lg[11, 0].item() and math.isinf(lg[11, 6].item()) else 1.0, 0.0))
+    # ce_rows directly: 101 columns (two 64-lane passes), padded leading dimensions, -inf in non-target columns, an all-equal row
+    S, V, ld = 77, 101, 104
+    gi = torch.Generator().manual_seed(620)
+    lgt = torch.full((S, ld), float("nan"))
+    lgt[:, :V] = 4.0 * torch.randn(S, V, generator=gi)
+    tgt = torch.randint(0, V, (S,), generator=gi)
+    minf = torch.rand(S, V, generator=gi) < 0.1
+    minf[torch.arange(S), tgt] = False
+    lgt[:, :V][minf] = float("-inf")
+    lgt[13, :V] = 1.25
+    l64 = lgt[:, :V].double().requires_grad_(True)
+    rows_ref = TF.cross_entropy(l64, tgt, reduction="none")
+    (dref,) = torch.autograd.grad(rows_ref.sum() * 1.7, l64)
+    for ddt in (torch.float32, torch.bfloat16):
+        dn = "fp32" if ddt == torch.float32 else "bf16"
+        dlog = torch.full((S, ld), float("nan"), dtype=ddt, device=DEV)
+        for flat in (False, True):
+            rows, corr = ops.ce_rows(lgt.to(DEV), tgt.to(torch.int32).to(DEV), V, ld, dlog, ld, 1.7, flat_wrong=flat)
+            mx = l64.detach().max(-1).values
+            cref = (l64.detach()[torch.arange(S), tgt] >= mx) & ~(flat & (l64.detach().min(-1).values == mx))
+            out.append((f"ce_rows V=101 ld=104 dlogits[{dn}] flat_wrong={flat}: correct rows (mismatches)", float((corr.cpu().bool() != cref).sum().item()), 0.0))
+        out.append((f"ce_rows V=101 ld=104 dlogits[{dn}] loss rows", err(rows, rows_ref), TOL32))
+        out.append((f"ce_rows V=101 ld=104 dlogits[{dn}] dlogits", err(dlog[:, :V], dref), tol_for(ddt)))
+        out.append((f"ce_rows V=101 ld=104 dlogits[{dn}] pad columns (non-zero elements)", float((dlog[:, V:] != 0).sum().item()), 0.0))
+    return out
+
+
 def check_adam():
     from oracle import wavlm_oracle as O
     out = []
@@ -1142,6 +1640,7 @@ GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
     "convstack": check_convstack, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
     "linear_ffn": check_linear_ffn, "activations": check_activations, "loss": check_loss, "adam": check_adam, "dropout_exact": check_dropout_exact,
+    "gumbel_vq": check_gumbel_vq, "sampled_negatives": check_sampled_negatives,
 }
 
 if __name__ == "__main__":

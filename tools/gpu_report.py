@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     groups = sys.argv[1:] or ["gemm", "layernorm", "rowops", "conv0", "convstack", "attention", "posconv",
-                              "linear_ffn", "loss", "adam"]
+                              "linear_ffn", "loss", "adam", "gumbel_vq", "sampled_negatives"]
     lines = []
     for g in groups:
         t0 = time.time()

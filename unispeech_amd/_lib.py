@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVLM_HIP_LIB") or os.path.join(_HERE, "lib", "libwavlm_hip.so")
 
 _lib = None
-ABI_VERSION = 24  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
+ABI_VERSION = 25  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
 
 F32, BF16 = 0, 1
 
@@ -146,8 +146,8 @@ SIGNATURES = {
                                           c_i32, c_vp]),
     "wavlm_l2norm_fwd": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_i32, c_f32, c_vp]),
     "wavlm_l2norm_bwd": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
-    "wavlm_ce_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_i64, c_f32, c_vp]),
-    "wavlm_gather_dot": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i32, c_vp]),
+    "wavlm_ce_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_i64, c_f32, c_i32, c_vp]),
+    "wavlm_gather_dot": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp]),
     "wavlm_rows_wsum": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "wavlm_bce_workspace_bytes": (c_u64, []),
     "wavlm_bce_logits": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_u64, c_vp]),
@@ -162,7 +162,7 @@ SIGNATURES = {
     "wavlm_mix_workspace_bytes": (c_u64, [c_i32, c_i64]),
     "wavlm_mix_utterances": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_vp, c_u64, c_vp]),
     "wavlm_gumbel_vq_partial_rows": (c_u64, [c_i64]),
-    "wavlm_gumbel_vq_fwd": (c_i32, [c_vp, c_i32, c_vp, c_u64, c_f32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "wavlm_gumbel_vq_fwd": (c_i32, [c_vp, c_i32, c_vp, c_u64, c_f32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wavlm_vq_perplexity": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "wavlm_gumbel_vq_bwd": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "wavlm_layer_saved_bytes": (c_u64, [C.POINTER(LayerDesc)]),

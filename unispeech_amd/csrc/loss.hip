@@ -39,16 +39,20 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const TO* __restrict__ 
 }
 
 // per row: loss = lse(logits) - logits[target]; correct = logits[target] >= max; dlogits = w * (softmax - onehot)
+// flat_wrong: a row whose V logits are all equal is not correct -- Wav2vecCriterion counts (argmax == 0) minus
+// (argmax == 0 and argmin == 0) (criterions/wav2vec_criterion.py:105-113), and with the target in column 0 the first
+// arg-min is 0 exactly when nothing in the row is below the maximum (a masked -inf column is below it)
 template <typename TO>
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int* __restrict__ target,
     float* __restrict__ loss_rows, float* __restrict__ correct_rows, TO* __restrict__ dlogits, long S, int V, long ldl,
-    long ldd, float weight) {
+    long ldd, float weight, int flat_wrong) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (long row = (long)blockIdx.x * 4 + wave; row < S; row += (long)gridDim.x * 4) {
     const float* lr = logits + row * ldl;
-    float mx = -INFINITY;
-    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lr[c]);
+    float mx = -INFINITY, nmn = -INFINITY;  // nmn = -min
+    for (int c = lane; c < V; c += 64) { mx = fmaxf(mx, lr[c]); nmn = fmaxf(nmn, -lr[c]); }
     mx = wave_max(mx);
+    const bool flat = flat_wrong && !(-wave_max(nmn) < mx);
     float sum = 0.f;
     for (int c = lane; c < V; c += 64) sum += expf(lr[c] - mx);
     sum = wave_sum(sum);
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     const float lt = valid ? lr[t] : __builtin_nanf("");
     if (lane == 0) {
       loss_rows[row] = (mx + logf(sum)) - lt;
-      correct_rows[row] = (lt >= mx) ? 1.f : 0.f;
+      correct_rows[row] = (lt >= mx && !flat) ? 1.f : 0.f;
     }
     if (dlogits) {
       const float inv = 1.f / sum;
@@ -96,11 +100,15 @@ __global__ void sum_finish_kernel(const double* part, int n, float* out) {
 // The reference gathers the sampled rows into [N, S, C] (1.4 GB fp32 at cfg2-like sizes) and calls
 // cosine_similarity; here rows are L2-normalised once and every logit is one gathered dot product.
 // out[s, n] = scale * <X[s], Y[idx[s, n]]>     (one wave per s; lane l owns elements 4l .. 4l+3 of up to 4 chunks)
-// mask_equal: columns n >= 1 whose gathered row equals the row of column 0 (the positive) get -inf -- wav2vec 2.0's
-// `neg_is_pos` rule (models/wav2vec/wav2vec2.py:535-551) for quantised targets that repeat
+// Yraw != NULL: columns n >= 1 whose gathered row equals the row of column 0 (the positive) get -inf -- wav2vec 2.0's
+// `neg_is_pos` rule (models/wav2vec/wav2vec2.py:535-551) for quantised targets that repeat.  The reference compares the
+// rows BEFORE normalisation (Yraw); a positive multiple of the positive has the same normalised row and is not masked.
+// Equal raw rows have equal normalised rows, so the raw rows are read only for the few columns whose normalised row
+// (already in registers for the dot product) matches.
 template <typename T>
 __global__ __launch_bounds__(256) void gather_dot_kernel(const T* __restrict__ X, const T* __restrict__ Y,
-    const int* __restrict__ idx, float* __restrict__ out, long S, int N, int D, float scale, int mask_equal) {
+    const T* __restrict__ Yraw, const int* __restrict__ idx, float* __restrict__ out, long S, int N, int D, float scale) {
+  const int mask_equal = Yraw != nullptr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv = D >> 2;  // float4 groups per row
   for (long s = (long)blockIdx.x * 4 + wave; s < S; s += (long)gridDim.x * 4) {
@@ -129,7 +137,20 @@ __global__ __launch_bounds__(256) void gather_dot_kernel(const T* __restrict__ X
           }
         }
       a = wave_sum(a);
-      const bool all_same = mask_equal && n > 0 && __all(same);
+      bool all_same = mask_equal && n > 0 && __all(same);
+      if (all_same && j != j0) {  // wave-uniform
+        bool raw_same = true;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (lane + 64 * c < nv) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const long o = (lane + 64 * c) * 4 + e;
+              raw_same = raw_same && (Elem<T>::ld(Yraw + j * D + o) == Elem<T>::ld(Yraw + j0 * D + o));
+            }
+          }
+        all_same = __all(raw_same);
+      }
       if (lane == 0) out[s * N + n] = all_same ? -INFINITY : a * scale;
     }
   }
@@ -301,7 +322,7 @@ int wavlm_l2norm_bwd(const void* dy, const void* y, int32_t y_dtype, const float
 
 int wavlm_ce_rows(const float* logits, const int32_t* target, float* loss_rows, float* correct_rows, void* dlogits,
                   int32_t d_dtype, int64_t S, int32_t V, int64_t ld_logits, int64_t ld_dlogits, float weight,
-                  void* stream) {
+                  int32_t flat_wrong, void* stream) {
   if (!logits || !target || !loss_rows || !correct_rows || S < 0 || V <= 0 || ld_logits < V) return WL_EINVAL;
   if (dlogits && ld_dlogits < V) return WL_EINVAL;
   if (S == 0) return WL_OK;
@@ -309,10 +330,10 @@ int wavlm_ce_rows(const float* logits, const int32_t* target, float* loss_rows, 
   long grid = (S + 3) / 4; if (grid > 8192) grid = 8192;
   if (!dlogits || d_dtype == WL_F32)
     WL_LAUNCH((ce_rows_kernel<float>), dim3((unsigned)grid), dim3(256), 0, st, logits, target, loss_rows,
-                       correct_rows, (float*)dlogits, (long)S, (int)V, (long)ld_logits, (long)ld_dlogits, weight);
+                       correct_rows, (float*)dlogits, (long)S, (int)V, (long)ld_logits, (long)ld_dlogits, weight, (int)flat_wrong);
   else if (d_dtype == WL_BF16)
     WL_LAUNCH((ce_rows_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, st, logits, target, loss_rows,
-                       correct_rows, (bf16_t*)dlogits, (long)S, (int)V, (long)ld_logits, (long)ld_dlogits, weight);
+                       correct_rows, (bf16_t*)dlogits, (long)S, (int)V, (long)ld_logits, (long)ld_dlogits, weight, (int)flat_wrong);
   else return WL_EINVAL;
   return wl_check_launch();
 }
@@ -329,13 +350,13 @@ int wavlm_sum_f32(const float* x, int64_t n, float* out, void* workspace, uint64
 }
 
 int wavlm_gather_dot(const void* X, const void* Y, int32_t dtype, const int32_t* idx, float* out, int64_t S, int32_t N,
-                     int32_t D, float scale, int32_t mask_equal, void* stream) {
+                     int32_t D, float scale, const void* mask_raw, void* stream) {
   if (!X || !Y || !idx || !out || S < 0 || N <= 0 || D <= 0 || (D & 3) || D > 1024) return WL_EINVAL;
   if (S == 0) return WL_OK;
   hipStream_t st = (hipStream_t)stream;
   long grid = (S + 3) / 4; if (grid > 8192) grid = 8192;
-  if (dtype == WL_F32) WL_LAUNCH((gather_dot_kernel<float>), dim3((unsigned)grid), dim3(256), 0, st, (const float*)X, (const float*)Y, idx, out, (long)S, (int)N, (int)D, scale, (int)mask_equal);
-  else if (dtype == WL_BF16) WL_LAUNCH((gather_dot_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)Y, idx, out, (long)S, (int)N, (int)D, scale, (int)mask_equal);
+  if (dtype == WL_F32) WL_LAUNCH((gather_dot_kernel<float>), dim3((unsigned)grid), dim3(256), 0, st, (const float*)X, (const float*)Y, (const float*)mask_raw, idx, out, (long)S, (int)N, (int)D, scale);
+  else if (dtype == WL_BF16) WL_LAUNCH((gather_dot_kernel<bf16_t>), dim3((unsigned)grid), dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)Y, (const bf16_t*)mask_raw, idx, out, (long)S, (int)N, (int)D, scale);
   else return WL_EINVAL;
   return wl_check_launch();
 }

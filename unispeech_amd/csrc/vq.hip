@@ -32,7 +32,7 @@ __device__ __forceinline__ float vq_gumbel(unsigned long long seed, unsigned lon
 template <typename TL>
 __global__ __launch_bounds__(256) void gumbel_vq_fwd_kernel(const TL* __restrict__ logits, const float* __restrict__ noise,
     unsigned long long seed, float inv_tau, int training, long n, int G, int V, float* __restrict__ ysoft,
-    int* __restrict__ idx, float* __restrict__ part) {
+    int* __restrict__ idx, float* __restrict__ part, long ld_part) {
   const int lane = threadIdx.x & 63;
   const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (long)gridDim.x * 4;
   float accp[VQ_MAXG][VQ_MAXC], acch[VQ_MAXG][VQ_MAXC];
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void gumbel_vq_fwd_kernel(const TL* __restrict
     }
   }
   if (wid < nw) {
-    float* pp = part + wid * (2L * G * V);
+    float* pp = part + wid * ld_part;
 #pragma unroll
     for (int g = 0; g < VQ_MAXG; ++g) {
       if (g >= G) break;
@@ -208,16 +208,18 @@ extern "C" {
 uint64_t wavlm_gumbel_vq_partial_rows(int64_t n) { return (uint64_t)vq_grid(n) * 4; }
 
 int wavlm_gumbel_vq_fwd(const void* logits, int32_t dtype, const float* noise, uint64_t seed, float tau, int32_t training,
-                        int64_t n, int32_t G, int32_t V, float* ysoft, int32_t* idx, float* part, void* stream) {
+                        int64_t n, int32_t G, int32_t V, float* ysoft, int32_t* idx, float* part, int64_t ld_part,
+                        void* stream) {
   if (!logits || !idx || !part || n <= 0 || G < 1 || G > VQ_MAXG || V < 1 || V > 64 * VQ_MAXC || !(tau > 0.f)) return WL_EINVAL;
+  if (ld_part < 2L * G * V) return WL_EINVAL;
   if (training && !ysoft) return WL_EINVAL;
   const int grid = vq_grid(n);
   if (dtype == WL_F32)
     WL_LAUNCH(gumbel_vq_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)logits, noise,
-              (unsigned long long)seed, 1.f / tau, (int)training, (long)n, (int)G, (int)V, ysoft, idx, part);
+              (unsigned long long)seed, 1.f / tau, (int)training, (long)n, (int)G, (int)V, ysoft, idx, part, (long)ld_part);
   else
     WL_LAUNCH(gumbel_vq_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)logits, noise,
-              (unsigned long long)seed, 1.f / tau, (int)training, (long)n, (int)G, (int)V, ysoft, idx, part);
+              (unsigned long long)seed, 1.f / tau, (int)training, (long)n, (int)G, (int)V, ysoft, idx, part, (long)ld_part);
   return wl_check_launch();
 }
 

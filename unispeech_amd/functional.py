@@ -1224,18 +1224,20 @@ class SampledNegativesLossFn(torch.autograd.Function):
     """InfoNCE over sampled negatives (wav2vec 2.0 / UniSpeech: Wav2Vec2Model.compute_preds, models/wav2vec/wav2vec2.py:
     533-553, + Wav2vecCriterion's cross_entropy(logits, 0, 'sum'), criterions/wav2vec_criterion.py:44-64).
     x [S, C]: context projections; y [S, C]: targets; idx [S, 1 + N] int32 rows of y (column 0 = the positive, i.e. s
-    itself, then the sampled negatives); negatives equal to the positive are masked to -inf.  Returns
+    itself, then the sampled negatives); negatives whose un-normalised row equals the positive's are masked to -inf; a row
+    whose logits are all equal is not correct (the criterion's arg-min rule).  Returns
     (loss_sum[1], n_correct[1])."""
 
     @staticmethod
     def forward(ctx, x, y, idx, temp):
         S, N1 = idx.shape
         xn, inv_x = ops.l2norm_fwd(x.contiguous(), x.dtype)
-        yn, inv_y = ops.l2norm_fwd(y.contiguous(), y.dtype)
-        logits = ops.gather_dot(xn, yn, idx, 1.0 / temp, mask_equal=True)
+        yc = y.contiguous()
+        yn, inv_y = ops.l2norm_fwd(yc, y.dtype)
+        logits = ops.gather_dot(xn, yn, idx, 1.0 / temp, mask_raw=yc)
         target = torch.zeros(S, dtype=torch.int32, device=x.device)
         dlog = torch.empty((S, N1), dtype=torch.float32, device=x.device)
-        loss_rows, correct_rows = ops.ce_rows(logits, target, N1, N1, dlog, N1, 1.0)
+        loss_rows, correct_rows = ops.ce_rows(logits, target, N1, N1, dlog, N1, 1.0, flat_wrong=True)
         loss, ncorrect = ops.sum_f32(loss_rows), ops.sum_f32(correct_rows)
         ctx.save_for_backward(xn, yn, inv_x, inv_y, dlog, idx, x, y)
         ctx.temp = temp

@@ -700,14 +700,15 @@ def l2norm_bwd(dy, y, inv, x_dtype):
     return dx
 
 
-def ce_rows(logits, target, V, ld_logits, dlogits, ld_dlogits, weight):
+def ce_rows(logits, target, V, ld_logits, dlogits, ld_dlogits, weight, flat_wrong=False):
+    """flat_wrong: a row whose V logits are all equal is not correct (the wav2vec criterion's arg-min rule)"""
     dev = _dev(logits)
     S = target.numel()
     loss_rows = torch.empty(max(S, 1), dtype=torch.float32, device=dev)
     correct_rows = torch.empty(max(S, 1), dtype=torch.float32, device=dev)
     check(_lib.lib().wavlm_ce_rows(ptr(logits), ptr(target), ptr(loss_rows), ptr(correct_rows), ptr(dlogits),
                                    dt(dlogits) if dlogits is not None else 0, S, V, ld_logits, ld_dlogits,
-                                   float(weight), stream()), "wavlm_ce_rows")
+                                   float(weight), int(bool(flat_wrong)), stream()), "wavlm_ce_rows")
     return loss_rows[:S], correct_rows[:S]
 
 
@@ -800,14 +801,16 @@ def act_bwd(x, dy, kind):
     return dx
 
 
-def gather_dot(X, Y, idx, scale, mask_equal=False):
-    """out[s, n] = scale * <X[s], Y[idx[s, n]]>  (rows [., D], idx: int32 [S, N]); mask_equal: columns n >= 1 whose
-    gathered row equals the row of column 0 become -inf"""
-    dev = _dev(Y); _contig(X); _contig(Y); _contig(idx)
+def gather_dot(X, Y, idx, scale, mask_raw=None):
+    """out[s, n] = scale * <X[s], Y[idx[s, n]]>  (rows [., D], idx: int32 [S, N]); mask_raw: the rows of Y before
+    normalisation -- columns n >= 1 whose gathered row of mask_raw equals the row of column 0 become -inf"""
+    dev = _dev(Y); _contig(X); _contig(Y); _contig(idx); _contig(mask_raw)
+    if mask_raw is not None and (mask_raw.shape != Y.shape or mask_raw.dtype != Y.dtype):
+        raise ValueError("gather_dot: mask_raw must have the shape and dtype of Y")
     S, N = idx.shape
     out = torch.empty((S, N), dtype=torch.float32, device=dev)
     check(_lib.lib().wavlm_gather_dot(ptr(X), ptr(Y), dt(Y), ptr(idx), ptr(out), S, N, Y.shape[1], float(scale),
-                                      int(bool(mask_equal)), stream()), "wavlm_gather_dot")
+                                      ptr(mask_raw), stream()), "wavlm_gather_dot")
     return out
 
 
@@ -844,13 +847,14 @@ def gumbel_vq_fwd(logits, G, V, tau, training, noise=None, seed=0):
     n = logits.shape[0]
     L = _lib.lib()
     rows = int(L.wavlm_gumbel_vq_partial_rows(n))
-    part = torch.empty((rows, 2 * G * V), dtype=torch.float32, device=dev)
+    ldp = (2 * G * V + 7) // 8 * 8   # wavlm_colsum sums 8-column granules: pad columns are zero and dropped below
+    part = (torch.empty if ldp == 2 * G * V else torch.zeros)((rows, ldp), dtype=torch.float32, device=dev)
     idx = torch.empty(n * G, dtype=torch.int32, device=dev)
     ysoft = torch.empty((n * G, V), dtype=torch.float32, device=dev) if training else None
     check(L.wavlm_gumbel_vq_fwd(ptr(logits), dt(logits), ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, float(tau),
-                                int(bool(training)), n, int(G), int(V), ptr(ysoft), ptr(idx), ptr(part), stream()),
+                                int(bool(training)), n, int(G), int(V), ptr(ysoft), ptr(idx), ptr(part), ldp, stream()),
           "wavlm_gumbel_vq_fwd")
-    sums = colsum(part, torch.float32)
+    sums = colsum(part, torch.float32)[:2 * G * V]
     out = torch.empty(2, dtype=torch.float32, device=dev)
     dA = torch.empty(G * V, dtype=torch.float32, device=dev)
     check(L.wavlm_vq_perplexity(ptr(sums), n, int(G), int(V), ptr(out), ptr(dA), stream()), "wavlm_vq_perplexity")

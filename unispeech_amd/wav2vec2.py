@@ -393,8 +393,9 @@ class Wav2Vec2Model(nn.Module):
         (wav2vec2.py:738-741); -inf where a negative equals the positive"""
         h = net_output["head"]
         xn, _ = F.ops.l2norm_fwd(h["x"].detach().contiguous(), h["x"].dtype)
-        yn, _ = F.ops.l2norm_fwd(h["y"].detach().contiguous(), h["y"].dtype)
-        lg = F.ops.gather_dot(xn, yn, h["idx"], 1.0 / self.logit_temp, mask_equal=True)   # [S, N+1], row = b * Tm + t
+        yr = h["y"].detach().contiguous()
+        yn, _ = F.ops.l2norm_fwd(yr, yr.dtype)
+        lg = F.ops.gather_dot(xn, yn, h["idx"], 1.0 / self.logit_temp, mask_raw=yr)   # [S, N+1], row = b * Tm + t
         B, Tm = h["B"], h["Tm"]
         return lg.view(B, Tm, -1).transpose(0, 1).reshape(B * Tm, -1).float()
 
