@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 25
+#define WAVLM_HIP_ABI_VERSION 26
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -77,11 +77,41 @@ int wavlm_gemm(const wavlm_gemm_desc* d, void* stream);
  * extras, each with its own workspace) run as ONE grouped split-K launch + one slab reduction each -- the four dW of an
  * encoder layer (modules.py q/k/v/out_proj, WavLM.py:732-737 fc1/fc2) share the reduction length B*T; anything else is
  * executed as n wavlm_gemm calls.  Results are identical either way.  Callers should pick `split_k` so that all members' tiles x
- * split_k fit ONE round of the persistent grid (256 CUs minus wavlm_set_reserved_cus: what unispeech_amd/ops.py grouped_split
- * and csrc/layer.hip do).  Under WAVLM_WGRAD_STREAMK=1 `split_k` may be one larger than that (= the fp32 slabs the workspace
- * holds): the library then runs a balanced partition in which the CUs the one-round split leaves idle take the K tail of
- * every tile (measured neutral: off by default). */
+ * split_k fit ONE round of the persistent grid (256 CUs minus wavlm_set_reserved_cus): wavlm_slabs_grouped below says how many,
+ * and wavlm_linear_wgrads does all of it.  In the lab build under WAVLM_WGRAD_STREAMK=1 `split_k` may be one larger than that
+ * (= the fp32 slabs the workspace holds): the library then runs a balanced partition in which the CUs the one-round split
+ * leaves idle take the K tail of every tile (measured neutral: off by default). */
 int wavlm_gemm_grouped(const wavlm_gemm_desc* d, int32_t n, void* stream);
+
+/* Launch policy of the weight-gradient GEMMs (csrc/split_policy.hpp; host functions, no GPU needed).  tiles = 256 x 256
+ * output tiles, ktiles = 64-row steps of the reduction.  grid = 0, forced < 0, balanced < 0 ask for the process's own
+ * settings: 256 minus wavlm_set_reserved_cus, WAVLM_WGRAD_SPLIT, and "lab build with WAVLM_WGRAD_STREAMK" (both variables
+ * are read once per process; empty or 0 = unset).  Explicit values evaluate the same arithmetic anywhere.
+ *   wavlm_grid_blocks     blocks of a persistent GEMM grid
+ *   wavlm_split_single    split_k of one dW[M, N] launch
+ *   wavlm_split_grouped   split_k that keeps a grouped launch within ONE round of the grid; 0 = run the members singly
+ *   wavlm_slabs_grouped   `split_k` of a grouped launch's members = fp32 slabs per member (one more for the balanced launch)
+ *   wavlm_wgrad_grouping  0 iff WAVLM_WGRAD_GROUPING=0: every weight gradient goes out as a single launch */
+int32_t wavlm_grid_blocks(void);
+int32_t wavlm_split_single(int32_t M, int32_t N, int64_t ktiles, int32_t grid);
+int32_t wavlm_split_grouped(int64_t tiles, int64_t ktiles, int32_t grid, int32_t forced);
+int32_t wavlm_slabs_grouped(int64_t tiles, int64_t ktiles, int32_t grid, int32_t forced, int32_t balanced);
+int32_t wavlm_wgrad_grouping(void);
+
+/* dW_i[N_i, K_i] += dy_i[rows, N_i]^T x_i[rows, K_i] for the linears of one block (bf16 operands, dW in c_dtype; F.linear's
+ * weight gradient: modules.py q/k/v/out_proj, WavLM.py:732-737 fc1/fc2), issued under the policy above: consecutive items are
+ * packed into grouped launches of at most four while their tiles fit one round with a split >= 2, the rest run singly.
+ * wavlm_encoder_layer_bwd issues its four weight gradients through this call.  The workspace size is an upper bound over
+ * every packing and every CU reservation, so it stays valid if wavlm_set_reserved_cus is called between query and launch. */
+typedef struct wavlm_wgrad_item {
+  const void* dy;
+  const void* x;
+  void* dW;
+  int32_t N, K;
+} wavlm_wgrad_item;
+uint64_t wavlm_linear_wgrads_workspace_bytes(const wavlm_wgrad_item* items, int32_t n_items, int64_t rows);
+int wavlm_linear_wgrads(const wavlm_wgrad_item* items, int32_t n_items, int64_t rows, int32_t c_dtype, void* workspace,
+                        uint64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Row kernels (one 64-lane wave per row, wave-shuffle reductions).

@@ -70,19 +70,18 @@ def test_exact_fit_has_no_plan():
 
 
 def test_grouped_slabs(monkeypatch):
-    monkeypatch.delenv("WAVLM_WGRAD_SPLIT", raising=False)
+    # (grid, forced split and balanced flag passed explicitly: the library's own rules, evaluated without a lab library)
     monkeypatch.setenv("WAVLM_WGRAD_STREAMK", "1")
-    monkeypatch.setattr(ops, "lab_build", lambda: False)
-    assert ops.grouped_slabs(108, 375, 256) == 2     # the product library has no balanced launch: the switch alone does nothing
-    # pointing WAVLM_HIP_LIB at a PRODUCT build elsewhere must not change that (the capability is asked of the loaded
-    # library -- the lab build alone exports `wavlm_lab_build` --, not inferred from the variable)
+    assert ops.grouped_slabs(108, 375, 256, 0) == 2  # the product library has no balanced launch: the switch alone does nothing
+    # pointing WAVLM_HIP_LIB at a PRODUCT build elsewhere must not change that (the capability is the loaded
+    # library's own knowledge -- only the lab build is compiled with it --, not inferred from the variable)
     monkeypatch.setenv("WAVLM_HIP_LIB", "/somewhere/else/libwavlm_hip.so")
-    assert ops.grouped_slabs(108, 375, 256) == 2
+    assert ops.grouped_slabs(108, 375, 256, 0) == 2
     monkeypatch.delenv("WAVLM_HIP_LIB")
-    monkeypatch.setattr(ops, "lab_build", lambda: True)   # (the lab library, round 5)
-    assert ops.grouped_slabs(108, 375, 256) == 3     # Base: all four weight gradients of a block: 2 main splits + the tail
-    assert ops.grouped_slabs(64, 500, 256) == 5      # Large: one more than the one-round split (used once CUs are reserved)
-    assert ops.grouped_slabs(9, 16, 256) == 2        # too little work to balance: the one-round split
+    lab = dict(grid=256, forced=0, balanced=True)            # (the lab library, round 5)
+    assert ops.grouped_slabs(108, 375, **lab) == 3   # Base: all four weight gradients of a block: 2 main splits + the tail
+    assert ops.grouped_slabs(64, 500, **lab) == 5    # Large: one more than the one-round split (used once CUs are reserved)
+    assert ops.grouped_slabs(9, 16, **lab) == 2      # too little work to balance: the one-round split
     monkeypatch.delenv("WAVLM_WGRAD_STREAMK")
-    assert ops.grouped_slabs(108, 375, 256) == 2     # default: the one-round split
-    assert ops.grouped_split(12, 1000, 250) == 20    # conv-stack weight gradient with 6 CUs left to RCCL: 240 of 250 blocks, one round
+    assert ops.grouped_slabs(108, 375, 256, 0, False) == 2   # default: the one-round split
+    assert ops.grouped_split(12, 1000, 250, 0) == 20 # conv-stack weight gradient with 6 CUs left to RCCL: 240 of 250 blocks, one round

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVLM_HIP_LIB") or os.path.join(_HERE, "lib", "libwavlm_hip.so")
 
 _lib = None
-ABI_VERSION = 25  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
+ABI_VERSION = 26  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
 
 F32, BF16 = 0, 1
 
@@ -43,6 +43,11 @@ class GemmDesc(C.Structure):
         ("workspace", c_vp), ("ws_bytes", c_u64),
         ("colsum", c_vp), ("colsum_dtype", c_i32), ("colsum_accumulate", c_i32),
     ]
+
+
+class WgradItem(C.Structure):
+    """wavlm_wgrad_item (include/wavlm_hip.h): dW[N, K] += dy[rows, N]^T x[rows, K]"""
+    _fields_ = [("dy", c_vp), ("x", c_vp), ("dW", c_vp), ("N", c_i32), ("K", c_i32)]
 
 
 class LayerDesc(C.Structure):
@@ -77,6 +82,13 @@ SIGNATURES = {
     "wavlm_gemm_workspace_bytes": (c_u64, [C.POINTER(GemmDesc)]),
     "wavlm_gemm": (c_i32, [C.POINTER(GemmDesc), c_vp]),
     "wavlm_gemm_grouped": (c_i32, [C.POINTER(GemmDesc), c_i32, c_vp]),
+    "wavlm_grid_blocks": (c_i32, []),
+    "wavlm_split_single": (c_i32, [c_i32, c_i32, c_i64, c_i32]),
+    "wavlm_split_grouped": (c_i32, [c_i64, c_i64, c_i32, c_i32]),
+    "wavlm_slabs_grouped": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    "wavlm_wgrad_grouping": (c_i32, []),
+    "wavlm_linear_wgrads_workspace_bytes": (c_u64, [C.POINTER(WgradItem), c_i32, c_i64]),
+    "wavlm_linear_wgrads": (c_i32, [C.POINTER(WgradItem), c_i32, c_i64, c_i32, c_vp, c_u64, c_vp]),
     "wavlm_layernorm_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_i32, c_i32,
                                     c_i32, c_f32, c_u64, c_f32, c_u64, c_vp]),
     "wavlm_layernorm_bwd_workspace_bytes": (c_u64, [c_i32]),

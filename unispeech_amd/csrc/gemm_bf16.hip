@@ -18,6 +18,7 @@
 #include <atomic>
 
 #include "gemm_common.hpp"
+#include "split_policy.hpp"
 
 #include "tile_loaders.hpp"
 
@@ -353,7 +354,7 @@ static double tile_efficiency(const wavlm_gemm_desc* d, int nbatch, int BM, int 
   const long tm = (d->M + BM - 1) / BM, tn = (d->N + BN - 1) / BN;
   const long tiles = tm * tn * nbatch * (d->split_k < 1 ? 1 : d->split_k);
   const double useful = ((double)d->M * d->N) / ((double)tm * BM * tn * BN);
-  const long G = 256 - wavlm_get_reserved_cus();
+  const long G = wl_policy::grid_blocks();
   return useful * (double)tiles / ((double)G * (double)((tiles + G - 1) / G));
 }
 
@@ -640,18 +641,14 @@ extern "C" int wavlm_gemm_grouped(const wavlm_gemm_desc* d, int32_t n, void* str
   // measured neutral at the launch and the step level (profiles/r04/ab_wgrad_balanced_*.txt).
   long tiles_all = 0;
   for (int i = 0; i < n; ++i) tiles_all += (long)((d[i].M + 255) / 256) * ((d[i].N + 255) / 256);
-  const int G = 256 - wavlm_get_reserved_cus();
-#if GEMM_LAB
-  static const bool sk_on = [] { const char* e = getenv("WAVLM_WGRAD_STREAMK"); return e && *e == '1'; }();
-#else
-  constexpr bool sk_on = false;   // (lab library only)
-#endif
+  const int G = wl_policy::grid_blocks();
+  const bool sk_on = wl_policy::streamk();   // (lab library only)
   const int ksteps = (d->K + 63) / 64;
   GemmSk plan;
   const bool sk = sk_on && w4_takes(d, true) && tiles_all * (long)ksteps >= 8l * G && gemm_sk_plan(tiles_all, ksteps, G, plan) &&
                   d->split_k >= plan.s + 1;
   if (sk) p.split_k = plan.s + 1;
-  else if (sk_on && !getenv("WAVLM_WGRAD_SPLIT") && G / tiles_all >= 2 && d->split_k == G / tiles_all + 1)
+  else if (sk_on && !wl_policy::forced_split() && G / tiles_all >= 2 && d->split_k == G / tiles_all + 1)
     p.split_k = (int)(G / tiles_all);   // the spare slab stays unused: the one-round split fills the grid or nothing is to be won
   int vb = 0;
   double flops = 0.0;

@@ -15,6 +15,7 @@
 #include <atomic>
 
 #include "common.hpp"
+#include "split_policy.hpp"
 #include "wavlm_hip.h"
 
 // ---- gradient listener: which slice of the caller's gradient arena has just received an accumulation (in stream order) ----
@@ -128,110 +129,13 @@ uint64_t lin_dx_colsum_ws(int64_t n, int K) {
   return wavlm_gemm_workspace_bytes(&g);
 }
 
-// ---- weight gradients: dW[N, K] += dy[n, N]^T x[n, K], grouped as unispeech_amd/functional.py WgradGroup does ----
-struct WG { const void* dy; const void* x; void* dW; int N, K; };
-
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; }
-
-// split-K factor of a grouped launch: the largest that keeps tiles * split within ONE round of the 256-block persistent
-// grid (measured: every extra round costs a slab store and a pipeline refill per CU); 0 = run the members singly
-// blocks of a persistent GEMM grid (== ops.grid_blocks): the data-parallel reducer keeps some CUs free for RCCL
-long grid_blocks() { return 256 - wavlm_get_reserved_cus(); }
-int grouped_split(long tiles, long ktiles) {
-  static const int forced = env_int("WAVLM_WGRAD_SPLIT", 0);
-  if (forced > 0) return forced < 2 ? 2 : forced;
-  long s = grid_blocks() / (tiles > 0 ? tiles : 1);
-  if (s > ktiles / 8) s = ktiles / 8;
-  if (s > 64) s = 64;
-  return s >= 2 ? (int)s : 0;
-}
-// `split_k` of a grouped launch's members = slabs per member: the one-round split; the balanced launch (gemm_common.hpp:
-// gemm_sk_plan, WAVLM_WGRAD_STREAMK=1) needs one more (== ops.grouped_slabs)
-#if defined(WAVLM_EXPERIMENTAL)
-// exported by the lab library ONLY: how ops.grouped_slabs learns that the balanced launch exists in the library it loaded
-// (it used to infer it from WAVLM_HIP_LIB being set, which is also how one points at a product build elsewhere)
-extern "C" int wavlm_lab_build(void) { return 1; }
-#endif
-int grouped_slabs(long tiles, long ktiles) {
-#if defined(WAVLM_EXPERIMENTAL)   // (the balanced launch exists only in the lab library)
-  static const bool sk = env_int("WAVLM_WGRAD_STREAMK", 0) != 0 && env_int("WAVLM_WGRAD_SPLIT", 0) <= 0;
-#else
-  constexpr bool sk = false;
-#endif
-  int split = grouped_split(tiles, ktiles); if (split < 2) split = 2;
-  const long G = grid_blocks();
-  if (sk && tiles < G && tiles * ktiles >= 8 * G) { const int s = (int)(G / tiles) + 1; if (s > split) split = s; }
-  return split;
-}
-int single_split(int M, int N, long ktiles) {
-  if (M >= 256 && N >= 256) {
-    const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-    long s = grid_blocks() / tiles; if (s < 1) s = 1;
-    if (s > ktiles / 8) s = ktiles / 8;
-    if (s > 64) s = 64;
-    return s < 1 ? 1 : (int)s;
-  }
-  const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-  long s = (768 + tiles - 1) / tiles;
-  if (s > ktiles) s = ktiles;
-  if (s < 1) s = 1;
-  return s > 64 ? 64 : (int)s;
-}
-void wg_desc(wavlm_gemm_desc& g, const WG& w, int64_t n, int pdt, int split) {
+// ---- weight gradients: dW[N, K] += dy[n, N]^T x[n, K] (wavlm_linear_wgrads, below) ----
+void wg_desc(wavlm_gemm_desc& g, const wavlm_wgrad_item& w, int64_t n, int pdt, int split) {
   gemm_base(g);
   g.c_dtype = pdt; g.M = w.N; g.N = w.K; g.K = (int32_t)n; g.transA = 1; g.transB = 1;
   g.lda = w.N; g.ldb = w.K; g.ldc = w.K; g.A = w.dy; g.B = w.x; g.C = w.dW; g.accumulate = 1; g.split_k = split;
 }
-uint64_t wg_ws_bytes(const WG* it, int cnt, int64_t n) {  // upper bound over every grouping the launcher may choose
-  uint64_t tot = 0;
-  const long kt = (long)((n + 63) / 64);
-  for (int i = 0; i < cnt; ++i) {
-    int s = single_split(it[i].N, it[i].K, kt);
-    const int gs = grouped_slabs((long)((it[i].N + 255) / 256) * ((it[i].K + 255) / 256), kt);  // alone in a group: the most slabs it can see
-    if (gs > s) s = gs;
-    tot += rup256((uint64_t)s * it[i].N * it[i].K * 4);
-  }
-  return tot;
-}
-int wgrads(const WG* it, int cnt, int64_t n, int pdt, void* ws, uint64_t wsb, void* stream) {
-  // anything but the literal "0" is on -- as unispeech_amd/functional.py reads it (atoi("auto") would be 0: the fused block
-  // would silently stop grouping while the composed path still groups, and the two paths would no longer issue the same kernels)
-  static const bool grouping = [] { const char* e = getenv("WAVLM_WGRAD_GROUPING"); return !(e && e[0] == '0' && !e[1]); }();
-  const long kt = (long)((n + 63) / 64);
-  int i = 0;
-  while (i < cnt) {
-    // greedy sub-group in arrival order: members whose tiles still fit one round with a split >= 2 (at most four)
-    int j = i; long tiles = 0;
-    while (grouping && j < cnt && j - i < 4) {
-      const long t = (long)((it[j].N + 255) / 256) * ((it[j].K + 255) / 256);
-      if (j > i && grouped_split(tiles + t, kt) < 2) break;
-      tiles += t; ++j;
-    }
-    if (j == i) j = i + 1;
-    const int m = j - i;
-    Carver c(ws, wsb);
-    if (m >= 2) {
-      const int split = grouped_slabs(tiles, kt);
-      wavlm_gemm_desc g[4];
-      for (int k = 0; k < m; ++k) {
-        wg_desc(g[k], it[i + k], n, pdt, split);
-        g[k].ws_bytes = wavlm_gemm_workspace_bytes(&g[k]);
-        g[k].workspace = c.take(g[k].ws_bytes);
-      }
-      if (!c.ok) return WL_EINVAL;
-      const int rc = wavlm_gemm_grouped(g, m, stream);
-      if (rc != WL_OK) return rc;
-    } else {
-      wavlm_gemm_desc g;
-      wg_desc(g, it[i], n, pdt, single_split(it[i].N, it[i].K, kt));
-      if (g.split_k > 1) { g.ws_bytes = wavlm_gemm_workspace_bytes(&g); g.workspace = c.take(g.ws_bytes); if (!c.ok) return WL_EINVAL; }
-      const int rc = wavlm_gemm(&g, stream);
-      if (rc != WL_OK) return rc;
-    }
-    i = j;
-  }
-  return WL_OK;
-}
+inline long wg_tiles(const wavlm_wgrad_item& w) { return (long)((w.N + 255) / 256) * ((w.K + 255) / 256); }
 
 #define RC(expr) do { const int rc_ = (expr); if (rc_ != WL_OK) return rc_; } while (0)
 
@@ -260,9 +164,9 @@ BwdWs carve_bwd(const wavlm_layer_desc* d, void* base, uint64_t cap) {
   w.cs_ws = c.take(w.cs_b); w.cs_ws2 = c.take(w.cs_b);
   w.attn_b = wavlm_attn_fused_bwd_workspace_bytes(d->B, d->H, d->T); w.attn_ws = c.take(w.attn_b);
   w.gate_b = wavlm_gate_bwd_workspace_bytes(d->H, 64); w.gate_ws = c.take(w.gate_b);
-  const WG it[4] = {{nullptr, nullptr, nullptr, d->D, d->F}, {nullptr, nullptr, nullptr, d->F, d->D},
-                    {nullptr, nullptr, nullptr, d->D, d->D}, {nullptr, nullptr, nullptr, 3 * d->D, d->D}};
-  w.wg_b = wg_ws_bytes(it, 4, (int64_t)n); w.wg_ws = c.take(w.wg_b);
+  const wavlm_wgrad_item it[4] = {{nullptr, nullptr, nullptr, d->D, d->F}, {nullptr, nullptr, nullptr, d->F, d->D},
+                                  {nullptr, nullptr, nullptr, d->D, d->D}, {nullptr, nullptr, nullptr, 3 * d->D, d->D}};
+  w.wg_b = wavlm_linear_wgrads_workspace_bytes(it, 4, (int64_t)n); w.wg_ws = c.take(w.wg_b);
   w.bytes = c.off;
   if (base && !c.ok) w.bytes = ~(uint64_t)0;
   return w;
@@ -270,7 +174,87 @@ BwdWs carve_bwd(const wavlm_layer_desc* d, void* base, uint64_t cap) {
 
 }  // namespace
 
+#if defined(WAVLM_EXPERIMENTAL)
+// exported by the lab library ONLY (a caller that points WAVLM_HIP_LIB somewhere can ask which build it loaded)
+extern "C" int wavlm_lab_build(void) { return 1; }
+#endif
+
 extern "C" {
+
+// ---- split_policy.hpp through the C ABI: grid = 0, forced < 0, balanced < 0 = this process's own settings
+static long grid_or(int32_t grid) { return grid > 0 ? grid : wl_policy::grid_blocks(); }
+static int forced_or(int32_t forced) { return forced >= 0 ? forced : wl_policy::forced_split(); }
+int32_t wavlm_grid_blocks(void) { return wl_policy::grid_blocks(); }
+int32_t wavlm_wgrad_grouping(void) { return wl_policy::grouping() ? 1 : 0; }
+int32_t wavlm_split_single(int32_t M, int32_t N, int64_t ktiles, int32_t grid) { return wl_policy::split_single(M, N, (long)ktiles, grid_or(grid)); }
+int32_t wavlm_split_grouped(int64_t tiles, int64_t ktiles, int32_t grid, int32_t forced) {
+  return wl_policy::split_grouped((long)tiles, (long)ktiles, grid_or(grid), forced_or(forced));
+}
+int32_t wavlm_slabs_grouped(int64_t tiles, int64_t ktiles, int32_t grid, int32_t forced, int32_t balanced) {
+  return wl_policy::slabs_grouped((long)tiles, (long)ktiles, grid_or(grid), forced_or(forced), balanced >= 0 ? balanced != 0 : wl_policy::streamk());
+}
+
+// Upper bound over every grouping the launcher may choose and every CU reservation it may run under: a member alone in a
+// group sees the most slabs, and no split grows when the grid shrinks, so the full grid bounds them (the balanced launch:
+// never more than grid / tiles + 1 slabs).
+uint64_t wavlm_linear_wgrads_workspace_bytes(const wavlm_wgrad_item* it, int32_t cnt, int64_t n) {
+  if (!it || cnt <= 0 || n <= 0) return 0;
+  uint64_t tot = 0;
+  const long kt = (long)((n + 63) / 64), G = wl_policy::kFullGrid;
+  const int forced = wl_policy::forced_split();
+  const bool balanced = wl_policy::streamk() && forced == 0;
+  for (int i = 0; i < cnt; ++i) {
+    const long t = wg_tiles(it[i]);
+    int s = wl_policy::split_single(it[i].N, it[i].K, kt, G);
+    const int gs = wl_policy::slabs_grouped(t, kt, G, forced, false);
+    if (gs > s) s = gs;
+    if (balanced && t < G && G / t + 1 > s) s = (int)(G / t) + 1;
+    tot += rup256((uint64_t)s * it[i].N * it[i].K * 4);
+  }
+  return tot;
+}
+
+// Members are packed, in arrival order, into groups of at most four whose tiles still fit ONE round of the persistent grid
+// with a split >= 2 (Base: all four dW of a block, 108 tiles; Large: fc2 | fc1 | out_proj + q|k|v, 64 tiles each -- out_proj
+// alone needs a split of 16: 16 fp32 slabs for a 1024 x 1024 output); a member left alone runs as a single launch.
+int wavlm_linear_wgrads(const wavlm_wgrad_item* it, int32_t cnt, int64_t n, int32_t pdt, void* ws, uint64_t wsb, void* stream) {
+  if (!it || cnt <= 0 || n <= 0 || (pdt != WL_BF16 && pdt != WL_F32)) return WL_EINVAL;
+  for (int i = 0; i < cnt; ++i)
+    if (!it[i].dy || !it[i].x || !it[i].dW || it[i].N <= 0 || it[i].K <= 0) return WL_EINVAL;
+  const long kt = (long)((n + 63) / 64);
+  int i = 0;
+  while (i < cnt) {
+    int j = i; long tiles = 0;
+    while (wl_policy::grouping() && j < cnt && j - i < 4) {
+      const long t = wg_tiles(it[j]);
+      if (j > i && wavlm_split_grouped(tiles + t, kt, 0, -1) < 2) break;
+      tiles += t; ++j;
+    }
+    if (j == i) j = i + 1;
+    const int m = j - i;
+    Carver c(ws, wsb);
+    if (m >= 2) {
+      const int split = wavlm_slabs_grouped(tiles, kt, 0, -1, -1);
+      wavlm_gemm_desc g[4];
+      for (int k = 0; k < m; ++k) {
+        wg_desc(g[k], it[i + k], n, pdt, split);
+        g[k].ws_bytes = wavlm_gemm_workspace_bytes(&g[k]);
+        g[k].workspace = c.take(g[k].ws_bytes);
+      }
+      if (!c.ok) return WL_EINVAL;
+      const int rc = wavlm_gemm_grouped(g, m, stream);
+      if (rc != WL_OK) return rc;
+    } else {
+      wavlm_gemm_desc g;
+      wg_desc(g, it[i], n, pdt, wavlm_split_single(it[i].N, it[i].K, kt, 0));
+      if (g.split_k > 1) { g.ws_bytes = wavlm_gemm_workspace_bytes(&g); g.workspace = c.take(g.ws_bytes); if (!c.ok) return WL_EINVAL; }
+      const int rc = wavlm_gemm(&g, stream);
+      if (rc != WL_OK) return rc;
+    }
+    i = j;
+  }
+  return WL_OK;
+}
 
 uint64_t wavlm_layer_saved_bytes(const wavlm_layer_desc* d) { return desc_ok(d) ? carve_saved(d, nullptr).bytes : 0; }
 
@@ -393,8 +377,8 @@ int wavlm_encoder_layer_bwd(const wavlm_layer_desc* d, void* stream) {
   RC(lin_dx(w.dqkv, d->Wqkv, dain, n, 3 * D, D, 0, nullptr, dxres, nullptr, pdt, nullptr, 0, stream));
 
   // ---- the four weight gradients (arrival order of the composed path: fc2, fc1, out_proj, q|k|v)
-  const WG it[4] = {{df, s.hact, d->dW2, D, F}, {w.du, s.x1, d->dW1, F, D}, {da, s.O, d->dWo, D, D}, {w.dqkv, ain, d->dWqkv, 3 * D, D}};
-  RC(wgrads(it, 4, n, pdt, w.wg_ws, w.wg_b, stream));
+  const wavlm_wgrad_item it[4] = {{df, s.hact, d->dW2, D, F}, {w.du, s.x1, d->dW1, F, D}, {da, s.O, d->dWo, D, D}, {w.dqkv, ain, d->dWqkv, 3 * D, D}};
+  RC(wavlm_linear_wgrads(it, 4, n, pdt, w.wg_ws, w.wg_b, stream));
 
   if (d->Wgate)
     RC(wavlm_gate_bwd(w.dgate, ain, d->Wgate, d->grep_a, s.ga, s.gb, dain, d->dWgate, d->dbgate, d->dgrep_a, d->B, d->T, d->H, 64,

@@ -45,12 +45,12 @@ def _rup(x, m):
 # with several consumers (3 per post-LN encoder layer).  WAVLM_CHAIN_CONSUMERS=0 restores one Function per consumer.
 CHAIN_CONSUMERS = os.environ.get("WAVLM_CHAIN_CONSUMERS", "1") == "1"
 # Grouped weight-gradient launches (WgradGroup): the four dW of an encoder layer as ONE split-K launch when their tiles fit
-# one round of the persistent grid with a split >= 2 (ops.grouped_split: Base yes, Large no).  Measured on one box, same
+# one round of the persistent grid with a split >= 2 (csrc/split_policy.hpp: Base yes, Large no).  Measured on one box, same
 # build (profiles/r03/envab_wg.txt): per layer 335 us + 4 x 7 us of slab reduction against 349 us + 4 x 13 us for the single
 # launches, -0.47 ms per step at Base.  (Round 2 had it off: its measurement compared 425 us against 401 us on another
-# build.)  WAVLM_WGRAD_GROUPING=0 / 1 forces single / grouped launches.
-_WG = os.environ.get("WAVLM_WGRAD_GROUPING", "auto")
-WGRAD_GROUPING = _WG != "0"
+# build.)  WAVLM_WGRAD_GROUPING=0 forces single launches: the library reads it, for this path (ops.wgrad_grouping) and the
+# fused block alike.
+WGRAD_GROUPING = None  # True / False: this path's own setting (the tests compare the two in one process)
 SINK_LISTENERS = []  # callables(tensor): told which arena slice a backward kernel has just accumulated into (dp.GradReducer)
 
 
@@ -149,8 +149,8 @@ def _linear_bwd_w(dy2d, x2d, w_dtype, out=None):
 
 
 class WgradGroup:
-    """Weight gradients of one encoder layer collected during its backward and issued as ONE grouped split-K launch
-    (ops.gemm_wgrad_grouped): the four dW of a layer share the reduction length B*T, and alone each needs a split of
+    """Weight gradients of one encoder layer collected during its backward and issued by ONE library call that groups them
+    into split-K launches (ops.linear_wgrads): the four dW of a layer share the reduction length B*T, and alone each needs a split of
     7-28 to fill the GPU (fp32 slabs, short K loops).  Members are added by `_param_grads` in backward order; the group
     fires when `expected` members have arrived, and `flush_wgrad_groups()` (optimizer step / reducer finish) fires
     whatever is left, so a member that never receives a gradient cannot strand the others."""
@@ -178,27 +178,8 @@ class WgradGroup:
         self.fired = True
         if self in WgradGroup.pending:
             WgradGroup.pending.remove(self)
-        # Members are packed, in arrival order, into sub-groups whose tiles still fit ONE round of the persistent grid
-        # with a split >= 2 (ops.grouped_split): Base: all four dW of a layer (108 tiles); Large: fc2 | fc1 | out_proj +
-        # q|k|v (64 tiles each) -- out_proj alone needs a split of 16 (16 fp32 slabs for a 1024 x 1024 output).
-        n = self.items[0][0].shape[0]
-        kt = (n + 63) // 64
-        tl = [((dy.shape[1] + 255) // 256) * ((x.shape[1] + 255) // 256) for dy, x, _ in self.items]
-        groups, cur, cur_t = [], [], 0
-        for it, t in zip(self.items, tl):
-            if cur and (n == 0 or ops.grouped_split(cur_t + t, kt) < 2 or len(cur) == 4):
-                groups.append(cur)
-                cur, cur_t = [], 0
-            cur.append(it)
-            cur_t += t
-        if cur:
-            groups.append(cur)
-        for grp in groups:
-            if len(grp) == 1 or n == 0:
-                for dy2d, x2d, out in grp:
-                    _linear_bwd_w(dy2d, x2d, out.dtype, out=out)
-            else:
-                ops.gemm_wgrad_grouped(grp, grp[0][2].dtype)
+        if self.items[0][0].shape[0] > 0:   # (no rows: the gradient contribution is zero)
+            ops.linear_wgrads(self.items)
         for sk in self.sinks:
             WgradGroup.deferred.discard(sk.data_ptr())
             _sink_written(sk)
@@ -236,7 +217,8 @@ def _param_grads(dy2d, x2d, W, b, has_bias, need_w, need_b, sink_w=None, sink_b=
         has_bias = False  # accumulated by the consuming LayerNorm's backward
     dW = db = None
     sw = sink_w if sink_w is not None else _sink(W)
-    if sw is not None and wgroup is not None and WGRAD_GROUPING and dy2d.dtype == torch.bfloat16:
+    if (sw is not None and wgroup is not None and dy2d.dtype == torch.bfloat16
+            and (ops.wgrad_grouping() if WGRAD_GROUPING is None else WGRAD_GROUPING)):
         wgroup.add(dy2d, x2d, sw.view(W.shape), sw)  # deferred: issued with the layer's other weight gradients
     elif sw is not None:
         _linear_bwd_w(dy2d, x2d, W.dtype, out=sw.view(W.shape))

@@ -111,11 +111,12 @@ def gemm(A, B, Cc, M, N, K, *, lda, ldb, ldc, transA=False, transB=False, KB=1, 
 
 def gemm_wgrad_grouped(items, w_dtype):
     """The weight gradients dW_i[N_i, K_i] (+)= dy_i[n, N_i]^T @ x_i[n, K_i] of several linears that share the row count
-    n, as one grouped split-K launch (wavlm_gemm_grouped).  items: [(dy2d, x2d, out)] with `out` accumulated into."""
+    n, as ONE grouped split-K launch (wavlm_gemm_grouped) whatever their tiles come to: the kernel checks and the A/B tools.
+    items: [(dy2d, x2d, out)] with `out` accumulated into.  (The training path is linear_wgrads.)"""
     dev = _dev(items[0][0])
     n = items[0][0].shape[0]
     tiles = sum(((dy.shape[1] + 255) // 256) * ((x.shape[1] + 255) // 256) for dy, x, _ in items)
-    split = grouped_slabs(tiles, (n + 63) // 64)  # (callers that only group when one round fits: WgradGroup.fire)
+    split = grouped_slabs(tiles, (n + 63) // 64)
     L = _lib.lib()
     descs = (GemmDesc * len(items))()
     need = []
@@ -142,61 +143,50 @@ def gemm_wgrad_grouped(items, w_dtype):
     check(L.wavlm_gemm_grouped(descs, len(items), stream()), "wavlm_gemm_grouped[%d]" % len(items))
 
 
-def grouped_split(tiles, ktiles, grid=None):
-    """split-K factor of a grouped weight-gradient launch, or 0 when the members should run as single launches.
-    Measured (profiles/r03/envab_wg.txt, Base: 108 tiles x 375 K-steps per layer, same box): ONE round of tiles * split work
-    items is what pays -- split 2 (216 items) 335 us per layer against 349 us for the four single launches + 28 us less slab
-    reduction; split 7 (2.95 rounds) 371 us and split 14 423 us although they balance the K-steps better: every extra round
-    costs a slab store and a pipeline refill per CU.  So: the largest split that still fits one round, and no grouping when
-    even split 2 does not (Large: 192 tiles).  WAVLM_WGRAD_SPLIT overrides (A/B measurements)."""
-    forced = os.environ.get("WAVLM_WGRAD_SPLIT")
-    if forced:
-        return max(2, int(forced))
-    grid = grid or grid_blocks()
-    s = min(grid // max(tiles, 1), ktiles // 8, 64)
-    return s if s >= 2 else 0
+def linear_wgrads(items):
+    """dW_i[N_i, K_i] += dy_i[n, N_i]^T @ x_i[n, K_i] for the linears of one block, in arrival order (wavlm_linear_wgrads:
+    the library packs them into grouped launches -- the call the fused block makes for its own four).  items: [(dy2d, x2d,
+    out)], bf16 operands, every `out` of one dtype and accumulated into."""
+    dev = _dev(items[0][0])
+    n = items[0][0].shape[0]
+    arr = (_lib.WgradItem * len(items))()
+    for w, (dy, x, out) in zip(arr, items):
+        if dy.shape[0] != n or x.shape[0] != n or dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or out.dtype != items[0][2].dtype:
+            raise ValueError("weight gradients of one call share the row count and the dtypes (bf16 operands)")
+        _contig(dy); _contig(x); _contig(out)
+        w.dy, w.x, w.dW, w.N, w.K = ptr(dy), ptr(x), ptr(out), dy.shape[1], x.shape[1]
+    L = _lib.lib()
+    need = int(L.wavlm_linear_wgrads_workspace_bytes(arr, len(items), n))
+    ws = workspace(dev, need, "gemm")
+    check(L.wavlm_linear_wgrads(arr, len(items), n, dt(items[0][2]), ptr(ws), need, stream()), "wavlm_linear_wgrads[%d]" % len(items))
 
 
+# Launch policy of the weight-gradient GEMMs: the library's (csrc/split_policy.hpp has the rules and their measurements).
+# grid = 0, forced = -1, balanced = -1: the process's own settings (CU reservation, WAVLM_WGRAD_SPLIT, lab build with
+# WAVLM_WGRAD_STREAMK); explicit values evaluate the same arithmetic.
 def grid_blocks():
-    """blocks of a persistent GEMM grid: one per CU minus what the data-parallel reducer keeps free for the RCCL kernels
-    (wavlm_set_reserved_cus).  Every split-K choice aims at ONE round of THIS many blocks: with 8 CUs reserved, the 252 work
-    items a 256-CU split produces run as a full round plus a round of four (measured: +17 % step time,
-    profiles/r04/reserved_cus_base_before.txt)."""
-    return 256 - get_reserved_cus()
+    """blocks of a persistent GEMM grid: one per CU minus what the data-parallel reducer keeps free (wavlm_set_reserved_cus)"""
+    return int(_lib.lib().wavlm_grid_blocks())
 
 
-def lab_build():
-    """the loaded library is the lab build (tools/probe/build_probe.py lab: -DWAVLM_EXPERIMENTAL): it alone exports
-    `wavlm_lab_build`, and it alone carries the balanced grouped launch -- asked of the library itself, so that the slab count
-    chosen here always equals csrc/layer.hip: grouped_slabs of the same library"""
-    return hasattr(_lib.lib(), "wavlm_lab_build")
+def pick_split(M, N, ktiles, grid=0):
+    """split-K factor of a single weight-gradient-shaped launch"""
+    return int(_lib.lib().wavlm_split_single(M, N, ktiles, grid or 0))
 
 
-def grouped_slabs(tiles, ktiles, grid=None):
-    """`split_k` of the members of a grouped weight-gradient launch = fp32 slabs each member's workspace holds: the one-round
-    split.  Lab library only (lab_build(): WAVLM_HIP_LIB = tools/probe/lib/libwavlm_hip_lab.so) with WAVLM_WGRAD_STREAMK=1: one more, so that
-    the library can hand the CUs that split leaves idle (Base: 108 tiles x 2 = 216 of 256) the K tail of every tile
-    (csrc/gemm_common.hpp: gemm_sk_plan) -- measured neutral (profiles/r04/ab_wgrad_balanced_*.txt: the launch is not bound by
-    how many CUs take part), so libwavlm_hip.so does not carry that path."""
-    grid = grid or grid_blocks()
-    split = max(2, grouped_split(tiles, ktiles, grid))
-    if (os.environ.get("WAVLM_WGRAD_STREAMK", "0") == "1" and lab_build() and not os.environ.get("WAVLM_WGRAD_SPLIT")
-            and tiles < grid and tiles * ktiles >= 8 * grid):
-        return max(split, grid // tiles + 1)
-    return split
+def grouped_split(tiles, ktiles, grid=0, forced=-1):
+    """split-K factor of a grouped weight-gradient launch, or 0 when the members should run as single launches"""
+    return int(_lib.lib().wavlm_split_grouped(tiles, ktiles, grid or 0, forced))
 
 
-def pick_split(M, N, ktiles, nbatch=1, target_blocks=768):
-    """split-K factor so that a small-output / long-reduction GEMM still fills 256 CUs.  Problems the 256 x 256
-    ping-pong kernel takes (one block per CU) aim at one full round of 256 blocks; the 128-wide kernel (two to three
-    blocks per CU) at `target_blocks`."""
-    if M >= 256 and N >= 256:
-        tiles = ((M + 255) // 256) * ((N + 255) // 256) * nbatch
-        s = max(1, grid_blocks() // tiles)
-        return max(1, min(s, ktiles // 8, 64))
-    tiles = ((M + 127) // 128) * ((N + 127) // 128) * nbatch
-    s = max(1, min(ktiles, (target_blocks + tiles - 1) // tiles))
-    return min(s, 64)
+def grouped_slabs(tiles, ktiles, grid=0, forced=-1, balanced=-1):
+    """`split_k` of the members of a grouped weight-gradient launch = fp32 slabs each member's workspace holds"""
+    return int(_lib.lib().wavlm_slabs_grouped(tiles, ktiles, grid or 0, forced, int(balanced)))
+
+
+def wgrad_grouping():
+    """False under WAVLM_WGRAD_GROUPING=0: every weight gradient goes out as a single launch"""
+    return bool(_lib.lib().wavlm_wgrad_grouping())
 
 
 # ---------------------------------------------------------------------------------------- row kernels
