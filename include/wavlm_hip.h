@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 26
+#define WAVLM_HIP_ABI_VERSION 27
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -638,6 +638,28 @@ int wavlm_attn_plain_fwd(const void* qkv, void* O, int32_t B, int32_t H, int32_t
                          float scale, void* stream);
 int wavlm_diar_estimate(const void* z, int32_t z_dtype, int64_t z_stride_b, int64_t ldz, int32_t B, int32_t T, int32_t S,
                         int32_t E, float* activities, void* vectors, int32_t v_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * sinc resampler (ABI 27, csrc/resample.hip): torchaudio.functional.resample with sinc_interpolation, the step in front of the
+ * upstream in downstreams/speaker_diarization/models/models.py:138,207 (`torchaudio.transforms.Resample(sr, 16000)` per chunk
+ * batch) and downstreams/speaker_verification/verification.py:46-49.  o = orig / gcd(orig, new), n = new / gcd, `width` the
+ * filter half-width in input samples (ceil(lowpass_filter_width * o / (min(o, n) * rolloff))).
+ *   y[b, f * n + i] = sum_{j < 2 width + 1} table[i][j] * x[b, f * o + first[i] + j - width],   x = 0 outside [0, len_b)
+ * for f * n + i < ceil(n * len_b / o); the rest of the row up to L_out = ceil(n * L / o) is written as zero.  len_b =
+ * lengths[b] clamped to [0, L] (int32 on the device), or L when lengths is NULL.
+ *   table  fp32 [n][2 width + 1] on the device: per phase, the taps of the dense 2 width + o filter that lie inside the window
+ *          (|t| < lowpass_filter_width), zero-filled; first int32 [n]: the dense index of table[i][0], at most o - 1.
+ *   x      [B, L] WL_F32, or 2 = int16 PCM (scaled by 1 / 32768 in the kernel); y [B, L_out] WL_F32 or WL_BF16; x_stride /
+ *          y_stride: row strides in elements (>= L / >= L_out).  Bytes of y outside the B x L_out view are not touched.
+ * fp32 fmaf in tap order, one thread per output and no reduction across threads: bitwise reproducible, and a row's result does
+ * not depend on B or on its position in the batch.  wavlm_resample_supported: 1 if the table (n * (2 width + 2) * 4 bytes <= 48
+ * KiB) and a tile of at least four frames (4 o + 2 width <= 8192 samples) fit the kernel's LDS budget; wavlm_resample_rows
+ * returns -1 for a ratio that is not.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_resample_supported(int32_t o, int32_t n, int32_t width);
+int wavlm_resample_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths,
+                        const float* table, const int32_t* first, int32_t o, int32_t n, int32_t width, void* y,
+                        int32_t y_dtype, int64_t y_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

@@ -12,6 +12,8 @@ The inference path of the reference's downstreams/speaker_diarization: `models/m
     one is shifted back), so a recording is ONE batch through the upstream and one through the head.
   * `chunk_recording`, `get_cl_sil`, `clustering`, `merge_acti_clslab`, `stitching`, `cluster`, `make_rttm`, `diarize` -- the
     host stage, numpy only.  `python -m unispeech_amd.diarization UPSTREAM.pt HEAD.pt CONFIG audio.wav`.
+  * `predict` / `diarize` with `input_rate = model.sr` take the recording at the config's rate (8 kHz in the released config):
+    chunks are cut at that rate and resampled to 16 kHz in one launch (unispeech_amd/resample.py), as the reference does.
 Inference only (eval mode, no dropout, no gradients).  No CPU path and no eager fall-back for the kernels: every tensor-sized
 step of the head is a libwavlm_hip.so entry point.  What torch does here is parameter-sized: the softmax of feature_weight
 and the concatenated q|k|v and read-out weights (none of it under functional.frozen_parameters()).
@@ -26,6 +28,7 @@ import torch.nn as nn
 from . import _lib
 from . import functional as F
 from . import ops
+from . import resample as _resample
 from .speaker import Upstream, UpstreamStates, frame_count
 
 __all__ = ["TransformerDiarization", "fix_state_dict", "chunk_recording", "get_cl_sil", "clustering", "merge_acti_clslab",
@@ -497,24 +500,35 @@ def recording_chunks(model, n_samples16, chunk_size):
     return [(s * up, e * up) for s, e in spans], new_frames
 
 
-def predict(model, wav16, chunk_size):
+def predict(model, wav16, chunk_size, input_rate=16000):
     """a recording as ONE batch: wav16 1-D 16 kHz mono -> (acti_list: the new frames of every chunk [chunk_len, S], svec
-    [chunks * S, E], chunk_len_list)"""
+    [chunks * S, E], chunk_len_list).  input_rate = model.sr (not 16000): the waveform is at the config's rate, as the
+    reference reads it -- it is cut into chunks in sr-rate samples and the equal-length chunks go through ONE resample launch
+    to 16 kHz (per chunk, not per recording: models.py:138,207 resamples each chunk batch, and the two differ round every seam)."""
     wav16 = torch.as_tensor(wav16)
     if wav16.dim() != 1:
         raise NotImplementedError("a waveform of shape %s: 16 kHz mono (1-D) is expected" % (tuple(wav16.shape),))
-    spans, chunk_len_list = recording_chunks(model, len(wav16), chunk_size)
+    if input_rate == 16000:
+        spans, chunk_len_list = recording_chunks(model, len(wav16), chunk_size)
+        chunks = [wav16[s:e] for s, e in spans]
+    elif input_rate == model.sr:
+        spans, chunk_len_list = chunk_recording(len(wav16), chunk_size, model.frame_shift, model.subsampling)
+        chunks = _resample.resample(torch.stack([wav16[s:e] for s, e in spans]), input_rate, 16000)
+    else:
+        raise NotImplementedError("input_rate=%r: the waveform is either at 16000 Hz or at the model's sr=%r (then it is "
+                                  "resampled chunk by chunk)" % (input_rate, model.sr))
     with torch.no_grad():
-        acts, vecs = model.batch_estimate([wav16[s:e] for s, e in spans])
+        acts, vecs = model.batch_estimate(chunks)
     acts, vecs = acts.float().cpu().numpy(), vecs.float().cpu().numpy()
     acti_list = [acts[i][len(acts[i]) - n:] for i, n in enumerate(chunk_len_list)]
     return acti_list, vecs.reshape(-1, vecs.shape[-1]), chunk_len_list
 
 
-def diarize(model, wav16, chunk_size, args=None, sampling_rate=None):
-    """16 kHz mono recording -> RTTM lines: one batched device call, then clustering, merge, stitching, median filter"""
+def diarize(model, wav16, chunk_size, args=None, sampling_rate=None, input_rate=16000):
+    """16 kHz mono recording (or one at the model's sr with input_rate = model.sr, see predict) -> RTTM lines: one batched
+    device call, then clustering, merge, stitching, median filter"""
     args = args or infer_args(num_speakers=model.n_speakers)
-    acti_list, svec, _ = predict(model, wav16, chunk_size)
+    acti_list, svec, _ = predict(model, wav16, chunk_size, input_rate)
     data = cluster(args, acti_list, svec)
     return make_rttm(args, data, model.frame_shift, model.subsampling, sampling_rate or model.sr)
 
@@ -543,6 +557,16 @@ def read_wav(path, sr_model):
         raise NotImplementedError("%s: sample rate %d; only 16 kHz input is taken (the reference resamples %d Hz audio with "
                                   "torchaudio's Resample, which is not built)" % (path, sr, sr_model))
     return torch.from_numpy(wav).float()
+
+
+def read_recording(path, sr_model):
+    """16-bit PCM mono at 16 kHz or at the config's sr -> (float32 tensor, rate); predict's input_rate takes the rate"""
+    from .kmeans import read_wav as _read
+    wav, sr = _read(path)
+    if sr not in (16000, sr_model):
+        raise NotImplementedError("%s: sample rate %d; the file must be at 16000 Hz or at the config's sr (%d Hz), which is "
+                                  "resampled chunk by chunk as the reference does" % (path, sr, sr_model))
+    return torch.from_numpy(wav).float(), sr
 
 
 def load_pair(upstream_path, head_path, conf):
@@ -585,9 +609,9 @@ def main(argv=None):
     model = load_pair(a.upstream, a.head, conf)
     if a.bf16:
         model = model.to(torch.bfloat16)
-    wav = read_wav(a.wav, conf["model"].get("sr", 8000))
+    wav, rate = read_recording(a.wav, conf["model"].get("sr", 8000))
     with torch.no_grad():
-        lines = diarize(model, wav.cuda(), conf["dataset"]["chunk_size"], a, conf["dataset"]["sampling_rate"])
+        lines = diarize(model, wav.cuda(), conf["dataset"]["chunk_size"], a, conf["dataset"]["sampling_rate"], input_rate=rate)
     with open(a.out_rttm_file, "w") as f:
         f.write("".join(line + "\n" for line in lines))
     print("wrote %d segments to %s" % (len(lines), a.out_rttm_file))

@@ -8,7 +8,8 @@ The inference path of the reference's downstreams/speaker_verification: `models/
     under `feature_extract.model.*`.
   * `hidden_states(wavs)` -- the L+1 states straight from the encoder (no hooks, no [T, B, D] copies), one upstream call per
     distinct waveform length; `forward_states(states, lengths)` -- the head alone; `forward(wavs)` -- both.
-  * `score(emb1, emb2)` -- cosine; `python -m unispeech_amd.speaker embed|verify UPSTREAM.pt HEAD.pt a.wav [b.wav]`.
+  * `score(emb1, emb2)` -- cosine; `python -m unispeech_amd.speaker embed|verify UPSTREAM.pt HEAD.pt a.wav [b.wav]` (a file
+    that is not at 16 kHz is resampled to it on the device, unispeech_amd/resample.py, as verification.py:46-49 does).
 Inference only (eval mode, BatchNorm running statistics, no gradients).  No CPU path and no eager fall-back for the kernels:
 every tensor-sized step of the head is a libwavlm_hip.so entry point.  What torch does here is small and parameter- or
 waveform-sized: the softmax of feature_weight, folding the BatchNorms and packing the Res2 weights (about 25 launches per call,
@@ -422,6 +423,19 @@ def read_wav_16k(path):
     return torch.from_numpy(wav).float()
 
 
+def read_wav(path):
+    """16-bit PCM at any rate (kmeans.read_wav; channels averaged) -> (float32 tensor, sample rate)"""
+    from .kmeans import read_wav as _read
+    wav, sr = _read(path)
+    return torch.from_numpy(wav).float(), sr
+
+
+def to_16k(wav, rate):
+    """verification.py:46-49: a file that is not at 16 kHz is resampled to it, here on the device (resample.py)"""
+    from .resample import resample
+    return resample(wav.cuda(), rate, 16000)
+
+
 def load_pair(upstream_path, head_path, emb_dim=256):
     """upstream checkpoint {'cfg', 'model'} + head checkpoint {'model': state dict} (the reference's
     fine-tuned file: head keys, optionally feature_extract.model.* as well) -> ECAPA_TDNN_SMALL on the device, eval mode"""
@@ -455,12 +469,12 @@ def parse_args(argv=None):
 def main(argv=None):
     a = parse_args(argv)
     paths = a.wavs if a.cmd == "embed" else [a.wav1, a.wav2]
-    wavs = [read_wav_16k(p) for p in paths]
+    wavs = [read_wav(p) for p in paths]
     model = load_pair(a.upstream, a.head, a.emb_dim)
     if a.bf16:
         model = model.to(torch.bfloat16)
     with torch.no_grad():
-        emb = model([w.cuda() for w in wavs])
+        emb = model([to_16k(w, sr) for w, sr in wavs])
     if a.cmd == "embed":
         for p, e in zip(paths, emb.float().cpu()):
             print(p, " ".join("%.6f" % v for v in e.tolist()))
