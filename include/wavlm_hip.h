@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 27
+#define WAVLM_HIP_ABI_VERSION 28
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -660,6 +660,30 @@ int wavlm_resample_supported(int32_t o, int32_t n, int32_t width);
 int wavlm_resample_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths,
                         const float* table, const int32_t* first, int32_t o, int32_t n, int32_t width, void* y,
                         int32_t y_dtype, int64_t y_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Kaldi MFCC + deltas (ABI 28, csrc/mfcc.hip): the 39-wide features of HuBERT's first k-means iteration
+ * (src/examples/hubert/simple_kmeans/dump_mfcc_feature.py:46-55: torchaudio.compliance.kaldi.mfcc(use_energy=False) at its
+ * defaults, compute_deltas twice, [c | d | dd]).  W = int(0.025 sr), S = int(0.010 sr), P = the next power of two >= W.
+ *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype 0 / 2; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
+ *   lengths  NULL or B sample counts (clamped to [0, L]): a row ends there
+ *   window [W], twiddle [P][2] = (cos, -sin)(2 pi t / P), mel_idx [23][3] = (first bin, count, offset into mel_w), mel_w
+ *   [n_mel_w <= P]: filter b = sum_i mel_w[offset + i] * power[first + i] over bins < P / 2; dct [13][23] with the lifter folded
+ *   in -- computed by the host in float64 and rounded to fp32 once (unispeech_amd/mfcc.py); out-of-range mel_idx entries are
+ *   clamped, never followed
+ *   y        fp32 [B, Mmax, ncol], ncol 39 or 13 (no deltas), row stride y_stride >= Mmax * ncol in elements; Mmax >=
+ *            wavlm_mfcc_frames(L, W, S); frames at or beyond a row's own count are written as zero; deltas replicate the row's
+ *            own first and last frame
+ * One launch, nothing staged in HBM.  Fixed arithmetic order: a row's features are bitwise the same wherever the row sits in the
+ * batch.  wavlm_mfcc_supported (host): 1 if P is a power of two in [64, 512], P / 2 < W <= P, 1 <= S <= W and the tile fits 80
+ * KiB of LDS (16000 Hz: 400 / 160 / 512 and 8000 Hz: 200 / 80 / 256 do); wavlm_mfcc_rows returns -1 otherwise.
+ * wavlm_mfcc_frames (host): 0 for len < W, else 1 + (len - W) / S.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_mfcc_supported(int32_t W, int32_t S, int32_t P);
+int64_t wavlm_mfcc_frames(int64_t len, int32_t W, int32_t S);
+int wavlm_mfcc_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
+                    int32_t S, int32_t P, const float* window, const float* twiddle, const int32_t* mel_idx, const float* mel_w,
+                    int32_t n_mel_w, const float* dct, float* y, int64_t y_stride, int64_t Mmax, int32_t ncol, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

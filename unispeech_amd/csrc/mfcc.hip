@@ -1,0 +1,305 @@
+// Kaldi MFCC + deltas (ABI 28): the features of HuBERT's first k-means iteration, what the reference computes per utterance on
+// the CPU in src/examples/hubert/simple_kmeans/dump_mfcc_feature.py:46-55 -- torchaudio.compliance.kaldi.mfcc(use_energy=False)
+// at its defaults, compute_deltas twice, [c | d | dd] = 39 columns.  With W = int(0.025 sr), S = int(0.010 sr), P = 2^ceil(log2 W):
+//   frame i = x[i S : i S + W], m = 1 + (len - W) / S frames;  minus its mean;  y[j] = x[j] - 0.97 x[max(j - 1, 0)];  times the
+//   Povey window;  zero-padded to P;  |rfft|^2;  23 mel filters (bins < P / 2);  log(max(E, 2^-23));  13 rows of DCT x lifter;
+//   d[t] = sum_{k = -2..2} k c[clamp(t + k, 0, m - 1)] / 10, applied twice.
+// Every table (window, twiddles exp(-2 pi i t / P), mel weights by filter, DCT x lifter) comes from the host, float64 rounded to
+// fp32 once (unispeech_amd/mfcc.py); no sine or cosine is evaluated here.
+//
+// One launch.  A workgroup of 4 waves owns MF_FT = 56 output frames of one row and computes the cepstra of MF_NF = 64 frames:
+// its own and 4 on either side, which is what the second-order delta reaches, so no cepstrum, spectrum or log-mel value ever
+// goes to HBM and nothing is exchanged between workgroups.  The (MF_NF - 1) S + W samples of the tile go to LDS once (int16
+// scaled by 1 / 32768, samples outside [0, len) as zero).  A wave takes one frame at a time: the real P-point transform is the
+// complex P / 2-point transform of z[n] = y[2n] + i y[2n + 1] -- Stockham radix-4 passes (one radix-2 pass when log2(P / 2) is
+// odd) between two wave-private LDS buffers, one butterfly per lane and pass at P = 512 -- and the split
+//   X[k] = (Z[k] + conj Z[H - k]) / 2 + w_P^k (Z[k] - conj Z[H - k]) / 2i,      H = P / 2, k < H
+// so an all-zero frame has an all-zero spectrum exactly and reaches the floor exactly.  Mel: one lane per filter runs over the
+// filter's own bins in order (480 weights at 16 kHz, not 23 x 257); DCT: one lane per coefficient, 23 fmaf's.
+// Arithmetic order is fixed and depends on nothing but the row's samples and the frame's index in the row (tiles start at frame
+// 0 of every row): a row's features are bit-identical wherever the row sits in the batch and whatever the other rows hold.
+#include "common.hpp"
+#include "../../include/wavlm_hip.h"
+
+#define MF_NT 256
+#define MF_WAVES 4
+#define MF_FT 56                       // output frames per workgroup
+#define MF_HALO 4                      // frames on either side the second-order delta reaches
+#define MF_NF (MF_FT + 2 * MF_HALO)    // frames whose cepstra a workgroup computes
+#define MF_ND (MF_FT + MF_HALO)        // frames whose first-order delta it computes
+#define MF_NMEL 23
+#define MF_NCEP 13
+#define MF_LDS_BYTES (80 * 1024)
+
+enum { MF_I16 = 2 };  // input only: 16-bit PCM
+
+// LDS carve-up in floats; the two float2 regions come first (8-byte alignment)
+struct mf_layout { int tw, fft, win, melw, meli, dct, x, c, d, total; };
+static inline __host__ __device__ mf_layout mf_carve(int W, int S, int P) {
+  mf_layout l;
+  l.tw = 0;                                  // float2 [P]
+  l.fft = l.tw + 2 * P;                      // per wave two buffers of float2 [P / 2]
+  l.win = l.fft + MF_WAVES * 2 * P;          // [W]
+  l.melw = l.win + W;                        // [P]: at most two filters per bin
+  l.meli = l.melw + P;                       // int [23][3]
+  l.dct = l.meli + 3 * MF_NMEL;              // [13][23]
+  l.x = l.dct + MF_NCEP * MF_NMEL;           // [(MF_NF - 1) S + W]
+  l.c = l.x + (MF_NF - 1) * S + W;           // [MF_NF][13]
+  l.d = l.c + MF_NF * MF_NCEP;               // [MF_ND][13]
+  l.total = l.d + MF_ND * MF_NCEP;
+  return l;
+}
+
+static inline int mf_supported(int64_t W, int64_t S, int64_t P) {
+  if (P < 64 || P > 512 || (P & (P - 1))) return 0;
+  if (W > P || 2 * W <= P || S < 1 || S > W) return 0;          // P is the next power of two at or above W
+  return (int64_t)mf_carve((int)W, (int)S, (int)P).total * 4 <= MF_LDS_BYTES;
+}
+
+static inline int64_t mf_frames(int64_t len, int64_t W, int64_t S) { return len < W ? 0 : 1 + (len - W) / S; }
+
+__device__ __forceinline__ float mf_load(const void* x, long i, int dt) {
+  return dt == MF_I16 ? (float)((const short*)x)[i] * (1.0f / 32768.0f) : ((const float*)x)[i];
+}
+
+// Butterflies are evaluated in fp64 registers on fp32 operands (samples, twiddles) and stored to LDS as fp32: a value is rounded
+// once per pass instead of once per multiply and add, which is what keeps the transform's error near that of a transform
+// evaluated exactly and rounded at the end (numpy's single-precision rfft, the tests' fp32 oracle, behaves like that)
+struct mf_c64 { double x, y; };
+__device__ __forceinline__ mf_c64 mf_wide(float2 a) { return {(double)a.x, (double)a.y}; }
+__device__ __forceinline__ float2 mf_narrow(double x, double y) { return make_float2((float)x, (float)y); }
+__device__ __forceinline__ mf_c64 mf_cmul(mf_c64 a, float2 w) {
+  return {a.x * (double)w.x - a.y * (double)w.y, a.x * (double)w.y + a.y * (double)w.x};
+}
+
+// sum_k k v[k + 2] / 10 as differences of the mirrored pairs: a constant stretch (digital silence at the floor) gives exactly 0
+__device__ __forceinline__ float mf_delta(const float* v) { return ((v[3] - v[1]) + 2.0f * (v[4] - v[0])) / 10.0f; }
+
+// one Stockham pass of radix R over H points: Ns = product of the radices before it; twiddles w_H^t = tw[2 t]
+template <int R>
+__device__ __forceinline__ void mf_pass(const float2* __restrict__ in, float2* __restrict__ out, const float2* __restrict__ tw,
+                                        int H, int Ns, int lane) {
+  const int T = H / R;
+  for (int j = lane; j < T; j += 64) {
+    const int k = j & (Ns - 1);
+    const int step = 2 * k * (H / (Ns * R));
+    mf_c64 v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = mf_wide(in[j + r * T]);
+#pragma unroll
+    for (int r = 1; r < R; ++r) v[r] = mf_cmul(v[r], tw[r * step]);
+    float2* o = out + (j - k) * R + k;
+    if (R == 2) {
+      o[0] = mf_narrow(v[0].x + v[1].x, v[0].y + v[1].y);
+      o[Ns] = mf_narrow(v[0].x - v[1].x, v[0].y - v[1].y);
+    } else {
+      const mf_c64 a0 = {v[0].x + v[2].x, v[0].y + v[2].y}, a1 = {v[0].x - v[2].x, v[0].y - v[2].y};
+      const mf_c64 a2 = {v[1].x + v[3].x, v[1].y + v[3].y};
+      const mf_c64 a3 = {v[1].y - v[3].y, v[3].x - v[1].x};                     // -i (v1 - v3)
+      o[0] = mf_narrow(a0.x + a2.x, a0.y + a2.y);
+      o[Ns] = mf_narrow(a1.x + a3.x, a1.y + a3.y);
+      o[2 * Ns] = mf_narrow(a0.x - a2.x, a0.y - a2.y);
+      o[3 * Ns] = mf_narrow(a1.x - a3.x, a1.y - a3.y);
+    }
+  }
+}
+
+__global__ __launch_bounds__(MF_NT) void mfcc_kernel(const void* __restrict__ x, int x_dt, long x_stride, long L,
+    const int* __restrict__ lengths, int W, int S, int P, const float* __restrict__ window, const float* __restrict__ twiddle,
+    const int* __restrict__ mel_idx, const float* __restrict__ mel_w, int n_mel_w, const float* __restrict__ dct,
+    float* __restrict__ y, long y_stride, long Mmax, int ncol) {
+  extern __shared__ __attribute__((aligned(16))) float mf_lds[];
+  const mf_layout lo = mf_carve(W, S, P);
+  const int H = P / 2;
+  float2* s_tw = (float2*)(mf_lds + lo.tw);
+  float* s_win = mf_lds + lo.win;
+  float* s_melw = mf_lds + lo.melw;
+  int* s_meli = (int*)(mf_lds + lo.meli);
+  float* s_dct = mf_lds + lo.dct;
+  float* s_x = mf_lds + lo.x;
+  float* s_c = mf_lds + lo.c;
+  float* s_d = mf_lds + lo.d;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y;
+  const long t0 = (long)blockIdx.x * MF_FT;                 // first output frame of the tile
+  long t1 = t0 + MF_FT;
+  if (t1 > Mmax) t1 = Mmax;
+  long len = L;
+  if (lengths) { const long l = lengths[b]; len = l < 0 ? 0 : (l < L ? l : L); }
+  const long m = len < W ? 0 : 1 + (len - W) / S;           // this row's frames; [m, Mmax) is written as zero
+  float* yrow = y + (size_t)b * y_stride;
+  if (t0 >= m) {                                            // nothing of the row reaches this tile
+    for (long q = t0 * ncol + tid; q < t1 * ncol; q += MF_NT) yrow[q] = 0.f;
+    return;
+  }
+  // tables
+  for (int k = tid; k < P; k += MF_NT) s_tw[k] = make_float2(twiddle[2 * k], twiddle[2 * k + 1]);
+  for (int k = tid; k < W; k += MF_NT) s_win[k] = window[k];
+  const int nw = n_mel_w < P ? n_mel_w : P;
+  for (int k = tid; k < P; k += MF_NT) s_melw[k] = k < nw ? mel_w[k] : 0.f;
+  if (tid < MF_NMEL) {                                      // a filter stays inside the H bins and the nw weights whatever it holds
+    int first = mel_idx[3 * tid], count = mel_idx[3 * tid + 1], off = mel_idx[3 * tid + 2];
+    first = first < 0 ? 0 : (first > H ? H : first);
+    off = off < 0 ? 0 : (off > nw ? nw : off);
+    if (count > H - first) count = H - first;
+    if (count > nw - off) count = nw - off;
+    if (count < 0) count = 0;
+    s_meli[3 * tid] = first; s_meli[3 * tid + 1] = count; s_meli[3 * tid + 2] = off;
+  }
+  for (int k = tid; k < MF_NCEP * MF_NMEL; k += MF_NT) s_dct[k] = dct[k];
+  // samples: s_x[k] = x[(t0 - MF_HALO) S + k]
+  const void* xrow = (const char*)x + (size_t)b * x_stride * (x_dt == MF_I16 ? 2 : 4);
+  const int span = (MF_NF - 1) * S + W;
+  const long g0 = (t0 - MF_HALO) * S;
+  for (int k = tid; k < span; k += MF_NT) {
+    const long g = g0 + k;
+    s_x[k] = (g >= 0 && g < len) ? mf_load(xrow, g, x_dt) : 0.f;
+  }
+  __syncthreads();
+
+  float2* bufA = (float2*)(mf_lds + lo.fft) + (size_t)wave * 2 * H;
+  float2* bufB = bufA + H;
+  // frames outside [0, m) are computed on whatever the tile holds there (zeros beyond the row) and never read: every wave makes
+  // the same number of trips, so the barriers below are uniform
+  for (int fr = wave; fr < MF_NF; fr += MF_WAVES) {
+    const float* xf = s_x + fr * S;
+    float part = 0.f;
+    for (int n = lane; n < W; n += 64) part += xf[n];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);
+    const float mean = part / (float)W;
+    for (int h = lane; h < H; h += 64) {
+      float2 z = make_float2(0.f, 0.f);
+      const int n = 2 * h;
+      if (n < W) {
+        const float cur = xf[n] - mean, prev = xf[n > 0 ? n - 1 : 0] - mean;
+        z.x = (cur - 0.97f * prev) * s_win[n];
+        if (n + 1 < W) z.y = ((xf[n + 1] - mean) - 0.97f * cur) * s_win[n + 1];
+      }
+      bufA[h] = z;
+    }
+    __syncthreads();
+    float2* src = bufA;
+    float2* dst = bufB;
+    int Ns = 1;
+    for (; Ns * 4 <= H; Ns *= 4) {
+      mf_pass<4>(src, dst, s_tw, H, Ns, lane);
+      __syncthreads();
+      float2* t = src; src = dst; dst = t;
+    }
+    if (Ns < H) {
+      mf_pass<2>(src, dst, s_tw, H, Ns, lane);
+      __syncthreads();
+      float2* t = src; src = dst; dst = t;
+    }
+    // power spectrum of the real transform, bins 0 .. H - 1 (the Nyquist bin has weight zero)
+    float* pw = (float*)dst;
+    for (int k = lane; k < H; k += 64) {
+      const mf_c64 zk = mf_wide(src[k]), zn = mf_wide(src[(H - k) & (H - 1)]);
+      const mf_c64 ev = {0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y)};             // (Z[k] + conj Z[H - k]) / 2
+      const mf_c64 od = {0.5 * (zk.y + zn.y), -0.5 * (zk.x - zn.x)};            // (Z[k] - conj Z[H - k]) / 2i
+      const mf_c64 t = mf_cmul(od, s_tw[k]);
+      const double re = ev.x + t.x, im = ev.y + t.y;
+      pw[k] = (float)(re * re + im * im);
+    }
+    __syncthreads();
+    float* lg = (float*)src;
+    if (lane < MF_NMEL) {
+      const int first = s_meli[3 * lane], count = s_meli[3 * lane + 1], off = s_meli[3 * lane + 2];
+      float e = 0.f;
+      for (int i = 0; i < count; ++i) e = fmaf(s_melw[off + i], pw[first + i], e);
+      lg[lane] = logf(fmaxf(e, 1.1920928955078125e-07f));
+    }
+    __syncthreads();
+    if (lane < MF_NCEP) {
+      float c = 0.f;
+#pragma unroll
+      for (int q = 0; q < MF_NMEL; ++q) c = fmaf(s_dct[lane * MF_NMEL + q], lg[q], c);
+      s_c[fr * MF_NCEP + lane] = c;
+    }
+    __syncthreads();
+  }
+
+  const long base = t0 - MF_HALO;                           // frame of s_c row 0
+  const long last = m - 1;
+  if (ncol > MF_NCEP) {
+    for (int q = tid; q < MF_ND * MF_NCEP; q += MF_NT) {    // d of frames t0 - 2 .. t0 + MF_FT + 1
+      const int ui = q / MF_NCEP, i = q - ui * MF_NCEP;
+      const long u = t0 - 2 + ui;
+      float d = 0.f;
+      if (u >= 0 && u <= last) {
+        float cv[5];
+#pragma unroll
+        for (int k = -2; k <= 2; ++k) {
+          long v = u + k;
+          v = v < 0 ? 0 : (v > last ? last : v);
+          cv[k + 2] = s_c[(int)(v - base) * MF_NCEP + i];
+        }
+        d = mf_delta(cv);
+      }
+      s_d[q] = d;
+    }
+    __syncthreads();
+  }
+  const int rows = (int)(t1 - t0);
+  for (int q = tid; q < rows * ncol; q += MF_NT) {
+    const int ti = q / ncol, col = q - ti * ncol;
+    const long t = t0 + ti;
+    float v = 0.f;
+    if (t <= last) {
+      if (col < MF_NCEP) {
+        v = s_c[(ti + MF_HALO) * MF_NCEP + col];
+      } else if (col < 2 * MF_NCEP) {
+        v = s_d[(ti + 2) * MF_NCEP + col - MF_NCEP];
+      } else {
+        const int i = col - 2 * MF_NCEP;
+        float dv[5];
+#pragma unroll
+        for (int k = -2; k <= 2; ++k) {
+          long u = t + k;
+          u = u < 0 ? 0 : (u > last ? last : u);
+          dv[k + 2] = s_d[(int)(u - (t0 - 2)) * MF_NCEP + i];
+        }
+        v = mf_delta(dv);
+      }
+    }
+    yrow[t0 * ncol + q] = v;
+  }
+}
+
+extern "C" {
+
+// 1 if wavlm_mfcc_rows takes this window / shift / transform size: P a power of two in [64, 512] and the next one at or above
+// W, 1 <= S <= W, and the tile fits the kernel's LDS budget
+int wavlm_mfcc_supported(int32_t W, int32_t S, int32_t P) { return mf_supported(W, S, P); }
+
+// frames of a row of `len` samples (snip_edges): 0 below W, else 1 + (len - W) / S; -1 for a window or shift below 1
+int64_t wavlm_mfcc_frames(int64_t len, int32_t W, int32_t S) {
+  if (W < 1 || S < 1) return -1;
+  return mf_frames(len < 0 ? 0 : len, W, S);
+}
+
+int wavlm_mfcc_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
+                    int32_t S, int32_t P, const float* window, const float* twiddle, const int32_t* mel_idx, const float* mel_w,
+                    int32_t n_mel_w, const float* dct, float* y, int64_t y_stride, int64_t Mmax, int32_t ncol, void* stream) {
+  if (!x || !y || !window || !twiddle || !mel_idx || !mel_w || !dct || B <= 0 || B > 65535 || L <= 0) return WL_EINVAL;
+  if (x_dtype != WL_F32 && x_dtype != MF_I16) return WL_EINVAL;
+  if (ncol != MF_NCEP && ncol != 3 * MF_NCEP) return WL_EINVAL;
+  if (!mf_supported(W, S, P) || n_mel_w < 0) return WL_EINVAL;
+  if (L > (INT64_MAX >> 8) || x_stride < L) return WL_EINVAL;
+  if (Mmax < mf_frames(L, W, S) || Mmax > (INT64_MAX >> 8) || y_stride < Mmax * ncol) return WL_EINVAL;   // no row is cut short
+  if (Mmax == 0) return WL_OK;
+  const int64_t tiles = (Mmax + MF_FT - 1) / MF_FT;
+  if (tiles > 0x7fffffffLL) return WL_EINVAL;
+  const size_t smem = (size_t)mf_carve(W, S, P).total * sizeof(float);
+  // set on every such call: the attribute is per device, and a flag kept here would be neither per device nor thread-safe
+  if (smem > 48 * 1024 &&
+      hipFuncSetAttribute((const void*)mfcc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS_BYTES) != hipSuccess)
+    return WL_ELAUNCH;
+  WL_LAUNCH(mfcc_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(MF_NT), smem, (hipStream_t)stream, x, (int)x_dtype,
+            (long)x_stride, (long)L, lengths, (int)W, (int)S, (int)P, window, twiddle, mel_idx, mel_w, (int)n_mel_w, dct, y,
+            (long)y_stride, (long)Mmax, (int)ncol);
+  return wl_check_launch();
+}
+
+}  // extern "C"

@@ -7,7 +7,9 @@ Replaces the reference's src/examples/hubert/simple_kmeans/ steps 2 and 3:
   * `ApplyKmeans`      -- dump_km_label.py:25-47, same call interface (numpy int64 labels); `assign` stays on the device.
   * `label_audio` / `dump_labels` -- dump_hubert_feature.py's chunked `get_feats` straight into the assignment, so no
     feature file is written; `dump_features` writes the reference's `.npy` / `.len` pair for interchange.
-`python -m unispeech_amd.kmeans {learn,dump_label,label_audio}` takes the reference scripts' positional arguments.
+  * `features="mfcc"` (`label_audio`, `dump_labels`, `dump_mfcc_features`) -- iteration 1 of the recipe, which has no model
+    yet: dump_mfcc_feature.py's 39-wide Kaldi MFCCs from the device op of unispeech_amd/mfcc.py (csrc/mfcc.hip).
+`python -m unispeech_amd.kmeans {learn,dump_label,label_audio,dump_mfcc}` takes the reference scripts' positional arguments.
 """
 import math
 import os
@@ -19,7 +21,7 @@ import torch
 from . import _lib
 
 __all__ = ["ApplyKmeans", "MiniBatchKMeans", "assign", "accumulate", "label_audio", "dump_labels", "dump_features",
-           "read_wav", "get_path_iterator"]
+           "dump_mfcc_features", "read_wav", "get_path_iterator"]
 
 
 def _stream():
@@ -367,10 +369,32 @@ def _normalize_flag(model, normalize):
     return bool(getattr(getattr(model, "cfg", None), "normalize", False))
 
 
-def label_audio(model, wav, layer, km, max_chunk=1_600_000, normalize=None):
+def _check_features(model, features):
+    if features not in (None, "mfcc"):
+        raise NotImplementedError("features=%r is not implemented (None: a model's layer states, 'mfcc')" % (features,))
+    if features == "mfcc" and model is not None:
+        raise ValueError("features='mfcc' takes model=None: the first iteration has no model")
+    if features is None and model is None:
+        raise ValueError("model=None needs features='mfcc'")
+
+
+def _mfcc_wave(wav):
+    """what dump_mfcc_feature.get_feats feeds kaldi.mfcc: the waveform as float32 (int16 PCM stays PCM), on the device"""
+    x = torch.as_tensor(wav)
+    if x.dtype != torch.int16:
+        x = x.to(torch.float32)
+    return x.reshape(-1).cuda()
+
+
+def label_audio(model, wav, layer, km, max_chunk=1_600_000, normalize=None, features=None, sample_rate=16000):
     """dump_hubert_feature.get_feats (chunks of max_chunk samples, output_layer=layer, layer_norm of the waveform when
-    the model's cfg.normalize is set) followed by the assignment, on the device: int32 labels, no host sync"""
+    the model's cfg.normalize is set) followed by the assignment, on the device: int32 labels, no host sync.
+    model=None, features="mfcc": dump_mfcc_feature.get_feats at `sample_rate` instead (layer, max_chunk, normalize unused)"""
+    _check_features(model, features)
     app = km if isinstance(km, ApplyKmeans) else ApplyKmeans(km)
+    if features == "mfcc":
+        from .mfcc import mfcc
+        return app.assign(mfcc(_mfcc_wave(wav), sample_rate)[0])
     feats = _get_feats(model, wav, layer, max_chunk, _normalize_flag(model, normalize))
     return app.assign(feats)
 
@@ -380,20 +404,52 @@ def _check_rate(path, sr, want=16000):
         raise ValueError("%s: sample rate %d, the model expects %d" % (path, sr, want))
 
 
-def dump_labels(tsv_dir, split, model, layer, km, nshard, rank, lab_dir, max_chunk=1_600_000, normalize=None):
+def _mfcc_batches(generator, sample_rate, max_batch_samples):
+    """the shard's waveforms (float32, on the device) in manifest order, grouped into lists whose padded size B * Lmax stays
+    within max_batch_samples (a longer utterance goes alone): one mfcc launch each"""
+    batch, longest = [], 0
+    for path, _ in generator():
+        wav, sr = read_wav(path)
+        _check_rate(path, sr, sample_rate)
+        if batch and (len(batch) + 1) * max(longest, len(wav)) > max_batch_samples:
+            yield batch
+            batch, longest = [], 0
+        batch.append(_mfcc_wave(wav))
+        longest = max(longest, len(wav))
+    if batch:
+        yield batch
+
+
+def _mfcc_utterances(generator, sample_rate, max_batch_samples):
+    """-> per utterance of the shard its [frames, 39] device features; a row's bits do not depend on the batch it was in"""
+    from .mfcc import mfcc
+    for batch in _mfcc_batches(generator, sample_rate, max_batch_samples):
+        feats, frames = mfcc(batch, sample_rate)
+        for r, n in enumerate(frames):
+            yield feats[r, :n]
+
+
+def dump_labels(tsv_dir, split, model, layer, km, nshard, rank, lab_dir, max_chunk=1_600_000, normalize=None, features=None,
+                sample_rate=16000, max_batch_samples=1 << 24):
     """waveforms of shard `rank` -> `{lab_dir}/{split}_{rank}_{nshard}.km` (dump_km_label.py's line format) and
-    `{lab_dir}/dict.km.txt`; no feature file"""
+    `{lab_dir}/dict.km.txt`; no feature file.  model=None, features="mfcc": waveform -> MFCC -> assignment, the shard's
+    utterances batched into launches of at most max_batch_samples padded samples (no label depends on the batching)"""
+    _check_features(model, features)
     app = km if isinstance(km, ApplyKmeans) else ApplyKmeans(km)
     norm = _normalize_flag(model, normalize)
     generator, _ = get_path_iterator(os.path.join(tsv_dir, split + ".tsv"), nshard, rank)
     os.makedirs(lab_dir, exist_ok=True)
     lab_path = os.path.join(lab_dir, "%s_%d_%d.km" % (split, rank, nshard))
     with open(lab_path, "w") as f:
-        for path, _ in generator():
-            wav, sr = read_wav(path)
-            _check_rate(path, sr)
-            lab = app.assign(_get_feats(model, wav, layer, max_chunk, norm)).cpu().numpy().astype(np.int64).tolist()
-            f.write(" ".join(map(str, lab)) + "\n")
+        if features == "mfcc":
+            for feat in _mfcc_utterances(generator, sample_rate, max_batch_samples):
+                f.write(" ".join(map(str, app.assign(feat).cpu().numpy().astype(np.int64).tolist())) + "\n")
+        else:
+            for path, _ in generator():
+                wav, sr = read_wav(path)
+                _check_rate(path, sr)
+                lab = app.assign(_get_feats(model, wav, layer, max_chunk, norm)).cpu().numpy().astype(np.int64).tolist()
+                f.write(" ".join(map(str, lab)) + "\n")
     with open(os.path.join(lab_dir, "dict.km.txt"), "w") as f:
         for i in range(app.centres.K):
             f.write("%d 1\n" % i)
@@ -404,15 +460,32 @@ def dump_features(tsv_dir, split, model, layer, nshard, rank, feat_dir, max_chun
     """dump_hubert_feature.dump_feature: `{split}_{rank}_{nshard}.npy` (fp32 [frames, D]) + `.len` (frames per utterance)"""
     norm = _normalize_flag(model, normalize)
     generator, _ = get_path_iterator(os.path.join(tsv_dir, split + ".tsv"), nshard, rank)
-    os.makedirs(feat_dir, exist_ok=True)
-    stem = os.path.join(feat_dir, "%s_%d_%d" % (split, rank, nshard))
-    raw = stem + ".npy.part"
-    total, width = 0, None
-    with open(raw, "wb") as rf, open(stem + ".len", "w") as lf:
+
+    def feats():
         for path, _ in generator():
             wav, sr = read_wav(path)
             _check_rate(path, sr)
-            feat = _get_feats(model, wav, layer, max_chunk, norm).float().cpu().numpy()
+            yield _get_feats(model, wav, layer, max_chunk, norm)
+
+    return _write_feature_shard(feats(), feat_dir, split, nshard, rank)
+
+
+def dump_mfcc_features(tsv_dir, split, sample_rate, nshard, rank, feat_dir, max_batch_samples=1 << 24):
+    """dump_mfcc_feature.dump_feature: the same `.npy` (fp32 [frames, 39]) / `.len` pair from the device MFCC op"""
+    generator, _ = get_path_iterator(os.path.join(tsv_dir, split + ".tsv"), nshard, rank)
+    return _write_feature_shard(_mfcc_utterances(generator, sample_rate, max_batch_samples), feat_dir, split, nshard, rank,
+                                width=39)
+
+
+def _write_feature_shard(feats, feat_dir, split, nshard, rank, width=None):
+    """per-utterance [frames, D] tensors -> `{split}_{rank}_{nshard}.npy` + `.len`, streamed through a raw part file"""
+    os.makedirs(feat_dir, exist_ok=True)
+    stem = os.path.join(feat_dir, "%s_%d_%d" % (split, rank, nshard))
+    raw = stem + ".npy.part"
+    total = 0
+    with open(raw, "wb") as rf, open(stem + ".len", "w") as lf:
+        for feat in feats:
+            feat = feat.float().cpu().numpy()
             width = feat.shape[1]
             rf.write(np.ascontiguousarray(feat, dtype="<f4").tobytes())
             total += feat.shape[0]
@@ -475,7 +548,12 @@ def load_model(ckpt_path):
     return model.cuda().eval()
 
 
-def main(argv=None):
+def _layer_arg(v):
+    """label_audio's LAYER: an integer, or '-' where --features mfcc makes it unused"""
+    return None if v == "-" else int(v)
+
+
+def _parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m unispeech_amd.kmeans")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -495,11 +573,21 @@ def main(argv=None):
     for a, t in (("feat_dir", str), ("split", str), ("km_path", str), ("nshard", int), ("rank", int), ("lab_dir", str)):
         p.add_argument(a, type=t)
     p = sub.add_parser("label_audio", help="waveforms -> .km labels, no feature dump")
-    for a, t in (("tsv_dir", str), ("split", str), ("ckpt_path", str), ("layer", int), ("km_path", str), ("nshard", int),
+    for a, t in (("tsv_dir", str), ("split", str), ("ckpt_path", str), ("layer", _layer_arg), ("km_path", str), ("nshard", int),
                  ("rank", int), ("lab_dir", str)):
         p.add_argument(a, type=t)
     p.add_argument("--max_chunk", default=1600000, type=int)
-    a = ap.parse_args(argv)
+    p.add_argument("--features", default=None, choices=["mfcc"], help="mfcc: iteration 1, ckpt_path and layer are ignored ('-')")
+    p.add_argument("--sample_rate", default=16000, type=int, help="with --features mfcc")
+    p = sub.add_parser("dump_mfcc", help="dump_mfcc_feature.py")
+    for a, t in (("tsv_dir", str), ("split", str), ("nshard", int), ("rank", int), ("feat_dir", str)):
+        p.add_argument(a, type=t)
+    p.add_argument("--sample_rate", default=16000, type=int)
+    return ap
+
+
+def main(argv=None):
+    a = _parser().parse_args(argv)
     if a.cmd == "learn":
         feat = load_feature(a.feat_dir, a.split, a.nshard, a.seed, a.percent)
         km = MiniBatchKMeans(n_clusters=a.n_clusters, init=a.init, max_iter=a.max_iter, batch_size=a.batch_size, tol=a.tol,
@@ -514,7 +602,14 @@ def main(argv=None):
         with open(os.path.join(a.lab_dir, "%s_%d_%d.km" % (a.split, a.rank, a.nshard)), "w") as f:
             for feat in generator():
                 f.write(" ".join(map(str, app(np.asarray(feat)).tolist())) + "\n")
+    elif a.cmd == "dump_mfcc":
+        dump_mfcc_features(a.tsv_dir, a.split, a.sample_rate, a.nshard, a.rank, a.feat_dir)
+    elif a.features == "mfcc":
+        dump_labels(a.tsv_dir, a.split, None, None, a.km_path, a.nshard, a.rank, a.lab_dir, features="mfcc",
+                    sample_rate=a.sample_rate)
     else:
+        if a.layer is None:
+            raise SystemExit("label_audio: LAYER '-' needs --features mfcc")
         dump_labels(a.tsv_dir, a.split, load_model(a.ckpt_path), a.layer, a.km_path, a.nshard, a.rank, a.lab_dir,
                     a.max_chunk)
 
