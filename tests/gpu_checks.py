@@ -204,8 +204,82 @@ def check_gemm_pp(variant=3, name="gemm_pp"):
         ops.gemm(x.to(dtype).to(DEV), Wf.to(dtype).to(DEV), y, Tout, Cout, k * Cin, lda=s * Cin, ldb=k * Cin, ldc=Cout,
                  batch=(Bb, 1), sA=(Tin * Cin, 0), sC=(Tout * Cout, 0))
         out.append((f"{name} overlapping-row conv1d k3 s2", err(y, refc), tol))
+        out += _gemm_conv_forms(name)
     finally:
         ops.gemm_set_variant(0)
+    return out
+
+
+def _gemm_conv_forms(name):
+    """The three launch kinds of ConvStackFn (forward, one stride phase of the data gradient, weight gradient), one launch
+    each with the addressing the autograd function uses, at B = 2, Cin = Cout = 512, k = 3, s = 2, T_in = 549 (T_out = 274:
+    one full 256-row tile plus a ragged one per utterance; fp = bp = 1).  The caller has forced the kernel variant."""
+    out = []
+    dtype, tol = torch.bfloat16, TOLBF
+    Bb, Tin, Cc, k, s = 2, 549, 512, 3, 2
+    Tout, J, fp, bp = F._conv_geometry(Tin, k, s)
+    Tp = fp + Tout + bp
+    x = q(gen(Bb, Tin, Cc, seed=41), dtype)
+    w = q(gen(Cc, Cc, k, seed=42, scale=1.0 / math.sqrt(Cc * k)), dtype)
+    bias = q(0.1 * gen(Cc, seed=43), dtype)
+    du = q(gen(Bb, Tout, Cc, seed=44), dtype)
+    gpv = q(0.5 + 0.3 * gen(Bb, Tin, Cc, seed=45), dtype)   # stands for the GELU' of the layer below (epilogue class 4)
+    xd = x.to(dtype).to(DEV)
+    edge = _edge_rows(Tout)
+    nan = float("nan")
+    # ---- forward form: overlapping A rows, one batch entry per utterance, bias, table GELU, GELU' to aux
+    pre = TF.conv1d(x.double().transpose(1, 2), w.double(), bias.double(), stride=s).transpose(1, 2).contiguous().requires_grad_(True)
+    act = TF.gelu(pre)
+    gp, = torch.autograd.grad(act.sum(), pre)
+    Wf = w.permute(0, 2, 1).reshape(Cc, k * Cc).contiguous()
+    y = torch.full((Bb, Tout, Cc), nan, dtype=dtype, device=DEV)
+    u = torch.full((Bb, Tout, Cc), nan, dtype=dtype, device=DEV)
+    ops.gemm(xd, Wf.to(dtype).to(DEV), y, Tout, Cc, k * Cc, lda=s * Cc, ldb=k * Cc, ldc=Cc, batch=(Bb, 1),
+             sA=(Tin * Cc, 0), sC=(Tout * Cc, 0), epi=3, aux=u, ld_aux=Cc, sAux=(Tout * Cc, 0), bias=bias.to(dtype).to(DEV))
+    out.append((f"{name} conv forward form (overlap+batch+bias+epi 3) C", err(y, act), tol))
+    out.append((f"{name} conv forward form C boundary rows", err(y[:, edge], act[:, edge]), tol))
+    out.append((f"{name} conv forward form aux (GELU')", err(u, gp), tol))
+    out.append((f"{name} conv forward form aux boundary rows", err(u[:, edge], gp[:, edge]), tol))
+    # ---- phase form: both stride phases into one NaN-filled output between guard rows
+    P = torch.zeros(Bb, Tp, Cc)
+    P[:, fp:fp + Tout] = du
+    Pd = P.to(dtype).to(DEV)
+    xr = torch.zeros(Bb, Tin, Cc, dtype=torch.float64, requires_grad=True)
+    dxr, = torch.autograd.grad(TF.conv1d(xr.transpose(1, 2), w.double(), stride=s), xr, du.double().transpose(1, 2))
+    refp = dxr * gpv.double()
+    G = 4
+    buf = gen(G + Bb * Tin + G, Cc, seed=46).to(dtype).to(DEV)
+    buf[G:G + Bb * Tin] = nan
+    before = buf.clone()
+    inner = buf[G:G + Bb * Tin]
+    gpd = gpv.to(dtype).to(DEV)
+    for r in range(s):
+        Jr = J[r]
+        Wb = torch.cat([w[:, :, r + s * (Jr - 1 - jj)].t() for jj in range(Jr)], dim=1).contiguous()   # [Cin, Jr * Cout], newest tap first
+        Mr = (Tin - r + s - 1) // s
+        ops.gemm(Pd, Wb.to(dtype).to(DEV), inner, Mr, Cc, Jr * Cc, lda=Cc, ldb=Jr * Cc, ldc=s * Cc, batch=(Bb, 1),
+                 a_off=(fp - Jr + 1) * Cc, sA=(Tp * Cc, 0), c_off=r * Cc, sC=(Tin * Cc, 0), epi=4, aux=gpd, aux_off=r * Cc,
+                 ld_aux=s * Cc, sAux=(Tin * Cc, 0))
+    got = inner.view(Bb, Tin, Cc)
+    out.append((f"{name} conv phase form (a_off+c_off+strided C+epi 4) all rows", err(got, refp), tol))
+    for r in range(s):
+        out.append((f"{name} conv phase form rows of phase {r}", err(got[:, r::s], refp[:, r::s]), tol))
+    edge_in = _edge_rows(Tin)
+    out.append((f"{name} conv phase form boundary rows", err(got[:, edge_in], refp[:, edge_in]), tol))
+    for nm, sl in (("before", slice(0, G)), ("after", slice(G + Bb * Tin, None))):
+        same = torch.equal(buf[sl].view(torch.int16), before[sl].view(torch.int16))
+        out.append((f"{name} conv phase form guard rows {nm} the output untouched", 0.0 if same else 1.0, 0.0))
+    # ---- weight-gradient form: both operands K-strided, overlapping rows in B, one K batch per utterance with a K tail
+    # in each (274 = 4 * 64 + 18), a_off past the front pad; the pad rows lie outside [0, K) and are poisoned
+    Pn = torch.full((Bb, Tp, Cc), nan)
+    Pn[:, fp:fp + Tout] = du
+    Pnd = Pn.to(dtype).to(DEV)
+    refw = torch.einsum("bto,btck->okc", du.double(), x.double().unfold(1, k, s)).reshape(Cc, k * Cc)
+    for split in (1, 3):
+        dWf = torch.full((Cc, k * Cc), nan, dtype=dtype, device=DEV)
+        ops.gemm(Pnd, xd, dWf, Cc, k * Cc, Tout, lda=Cc, ldb=s * Cc, ldc=k * Cc, transA=True, transB=True, a_off=fp * Cc,
+                 KB=Bb, sA_kb=Tp * Cc, sB_kb=Tin * Cc, split_k=split)
+        out.append((f"{name} conv weight-gradient form (tA+tB+overlap+KB+a_off) split={split}", err(dWf, refw), tol))
     return out
 
 
@@ -555,6 +629,217 @@ def check_convstack():
         out.append((tag + " dx", err(xd.grad, xr.grad), tol * 2))
         for i in range(len(specs)):
             out.append((tag + f" dW{i}", err(Wd[i].grad, Wr[i].grad), tol * 2))
+    return out
+
+
+# ---- the conv stack at production width: every launch of every layer on the 256 x 256 / 192 x 384 / four-wave tile kernels
+CONV_WIDE_C = 512
+CONV_WIDE_VARIANTS = (0, 3, 4, 5)   # ops.gemm_set_variant: automatic, 256 x 256 ping-pong, 192 x 384, four-wave 256 x 256
+CONVSTACK_WIDE_CASES = [  # B, T0, specs, also in fp32, conv bias, x.requires_grad
+    (3, 1101, ((3, 2), (3, 2)), True, False, True),           # odd T_in twice (1101 -> 550 -> 274); dW0 split 3, dW1 split 1
+    (2, 1100, ((3, 2), (2, 2)), False, False, True),          # even T_in into (3,2); odd T_in (549) into (2,2): bp = 1, fp = 0
+    (2, 1047, ((2, 2), (2, 2)), True, False, True),           # odd, odd (1047 -> 523 -> 261): the trailing frame is unused
+    (2, 1048, ((2, 2), (2, 2)), False, False, True),          # fpp = bpp = 0: the hand-off buffer without a fill
+    (2, 2203, ((3, 2), (3, 2), (2, 2)), False, False, True),  # the padded hand-off twice, with different (fp, bp)
+    (2, 513, ((3, 2),), False, False, True),                  # T_out = 256 exactly; phase rows 257 / 256
+    (2, 512, ((2, 2),), False, False, True),                  # T_out = 256; both phases exactly one tile
+    (3, 1101, ((3, 2), (3, 2)), False, True, True),           # bias in the forward epilogue; dbias = column sums over the padded buffer
+    (2, 1100, ((3, 2), (2, 2)), False, False, False),         # no dx: the early exit at layer 0, dW still right
+]
+
+
+def _edge_rows(T):
+    """the first two and the last two frames of an utterance"""
+    return sorted({0, 1, T - 2, T - 1})
+
+
+def conv_launch_shapes(T0, specs, C):
+    """(name, M, N, K, both operands K-strided) of every GEMM ConvStackFn launches for a stack of C -> C layers over T0
+    frames: forward, weight gradient and one data-gradient launch per stride phase of every layer"""
+    shapes = []
+    T_in = T0
+    for i, (k, s) in enumerate(specs):
+        T_out, J, _, _ = F._conv_geometry(T_in, k, s)
+        shapes.append((f"forward {i}", T_out, C, k * C, False))
+        shapes.append((f"dW{i}", C, k * C, T_out, True))
+        for r in range(s):
+            shapes.append((f"dx{i} phase {r}", (T_in - r + s - 1) // s, C, J[r] * C, False))
+        T_in = T_out
+    return shapes
+
+
+def conv_shape_guard(T0, specs, C):
+    """number of launches a forced tile kernel would hand back to the generic kernel without a word (gemm_pp_ok /
+    gemm_pp3_ok: M >= 256 resp. 192, N >= 128 resp. 192, K >= 64, 8-element rows)"""
+    return float(sum(1 for (_, M, N, K, tr) in conv_launch_shapes(T0, specs, C)
+                     if M < 256 or N < 192 or K < 64 or ((M % 8 or N % 8) if tr else K % 8)))
+
+
+def unused_trailing_frames(T_in, k, s):
+    """frames at the end of an utterance that no window of a (k, s) convolution covers: their gradient is exactly 0"""
+    return T_in - (s * ((T_in - k) // s) + k)
+
+
+def convstack_wide_inputs(case, dtype):
+    B, T0, specs, _, bias, _ = case
+    C = CONV_WIDE_C
+    x = q(gen(B, T0, C, seed=1), dtype)
+    Ws = [q(gen(C, C, k, seed=10 + i, scale=1.0 / math.sqrt(C * k)), dtype) for i, (k, s) in enumerate(specs)]
+    bs = [q(0.1 * gen(C, seed=20 + i), dtype) for i in range(len(specs))] if bias else []
+    T = T0
+    for (k, s) in specs:
+        T = (T - k) // s + 1
+    dy = q(gen(B, T, C, seed=5), dtype)
+    return x, Ws, bs, dy
+
+
+def convstack_wide_ref(inputs, specs, need_dx=True, round_dtype=None):
+    """conv1d -> gelu per layer in float64 with nothing rounded in between; autograd for dx, every dW and dbias.  Returns
+    {"y", "dx" (if need_dx), "dW0".., "dbias0"..}.
+    round_dtype: the pre-activation u and the activation of every layer are rounded through that dtype (straight-through)
+    -- the two approximations a bf16 device path has and the exact reference lacks (tests/test_convstack_ref.py)."""
+    x, Ws, bs, dy = inputs
+
+    def rnd(t):
+        return t if round_dtype is None else t + (t.detach().to(round_dtype).double() - t.detach())
+
+    xr = x.double().requires_grad_(need_dx)
+    Wr = [w.double().requires_grad_(True) for w in Ws]
+    br = [b.double().requires_grad_(True) for b in bs]
+    h = xr.transpose(1, 2)
+    for i, (k, s) in enumerate(specs):
+        h = rnd(TF.gelu(rnd(TF.conv1d(h, Wr[i], br[i] if br else None, stride=s))))
+    yr = h.transpose(1, 2)
+    names = (["dx"] if need_dx else []) + [f"dW{i}" for i in range(len(Wr))] + [f"dbias{i}" for i in range(len(br))]
+    grads = torch.autograd.grad(yr, ([xr] if need_dx else []) + Wr + br, dy.double())
+    res = {"y": yr.detach()}
+    res.update(zip(names, grads))
+    return res
+
+
+def conv_compare(tag, got, ref, T_tail, tol, out):
+    """results of one device run against the reference: every tensor on its own scale (y at tol, gradients at twice that);
+    y and dx also on the scale of the first / last two frames of every utterance alone, so that a wrong edge frame cannot
+    hide behind the tensor-wide maximum; dx of the frames no window covers (T_tail of them) exactly 0"""
+    for nm, r in ref.items():
+        t = tol if nm == "y" else 2 * tol
+        out.append((f"{tag} {nm}", err(got[nm], r), t))
+        if nm in ("y", "dx"):
+            rows = _edge_rows(r.shape[1])
+            out.append((f"{tag} {nm} boundary rows", err(got[nm][:, rows], r[:, rows]), t))
+    if T_tail > 0 and "dx" in ref:
+        out.append((f"{tag} dx unused trailing frame == 0", float((got["dx"][:, -T_tail:] != 0).sum().item()), 0.0))
+
+
+def _poison(nbytes):
+    """NaN into the memory the next torch.empty calls will be handed: the caching allocator has nothing free but the blocks
+    filled here (one for the large pool, one for the small), so a row a kernel fails to write reads as NaN, never as a lucky 0"""
+    torch.cuda.empty_cache()
+    for n in (int(nbytes), 1 << 20):
+        t = torch.full((n // 2,), float("nan"), dtype=torch.bfloat16, device=DEV)
+        del t
+
+
+def _poison_reaches_empty(nbytes):
+    _poison(nbytes)
+    t = torch.empty((int(nbytes) // 8,), dtype=torch.bfloat16, device=DEV)
+    s = torch.empty((1024,), dtype=torch.bfloat16, device=DEV)
+    ok = bool(t.isnan().all().item()) and bool(s.isnan().all().item())
+    return ("poisoned allocations: torch.empty hands out the NaN-filled memory", 0.0 if ok else 1.0, 0.0)
+
+
+def _convstack_wide_device(case, dtype, inputs):
+    B, T0, specs, _, _, need_dx = case
+    x, Ws, bs, dy = inputs
+    xd = x.to(dtype).to(DEV).requires_grad_(need_dx)
+    Wd = [w.to(dtype).to(DEV).requires_grad_(True) for w in Ws]
+    bd = [b.to(dtype).to(DEV).requires_grad_(True) for b in bs]
+    dyd = dy.to(dtype).to(DEV)
+    nbytes = 8 * x.numel() * xd.element_size() + (16 << 20)   # several times all temporaries of the forward or the backward
+    _poison(nbytes)
+    yd = F.ConvStackFn.apply(xd, specs, True, *Wd, *bd)
+    _poison(nbytes)
+    grads = torch.autograd.grad(yd, ([xd] if need_dx else []) + Wd + bd, dyd)
+    names = (["dx"] if need_dx else []) + [f"dW{i}" for i in range(len(Wd))] + [f"dbias{i}" for i in range(len(bd))]
+    res = {"y": yd.detach()}
+    res.update(zip(names, grads))
+    return res
+
+
+def check_convstack_wide():
+    """ConvStackFn at C = 512 and more than 256 frames out of the last layer, so that every forward, stride-phase and
+    weight-gradient launch is taken by the tile kernels production runs (DESIGN.md kernel table), against float64 conv1d ->
+    gelu: bf16 under the automatic dispatch and each forced tile kernel, two cases also in fp32 (gemm_f32.hip addresses the
+    same way).  Tolerances are check_convstack's; tests/test_convstack_ref.py shows what the reference's side of them is."""
+    out = [_poison_reaches_empty(64 << 20)]
+    try:
+        for case in CONVSTACK_WIDE_CASES:
+            B, T0, specs, also_f32, bias, need_dx = case
+            name = f"B={B} T0={T0} {'+'.join(f'({k},{s})' for k, s in specs)}" + (" bias" if bias else "") + ("" if need_dx else " no-dx")
+            out.append((f"convstack_wide {name}: launches below the tile kernels' shapes", conv_shape_guard(T0, specs, CONV_WIDE_C), 0.0))
+            tail = unused_trailing_frames(T0, *specs[0])
+            for dtype in (torch.bfloat16,) + ((torch.float32,) if also_f32 else ()):
+                inputs = convstack_wide_inputs(case, dtype)
+                ref = convstack_wide_ref(inputs, specs, need_dx)
+                for v in (CONV_WIDE_VARIANTS if dtype == torch.bfloat16 else (0,)):
+                    ops.gemm_set_variant(v)
+                    got = _convstack_wide_device(case, dtype, inputs)
+                    conv_compare(f"convstack_wide[{dtype}] {name} variant {v}", got, ref, tail, tol_for(dtype), out)
+    finally:
+        ops.gemm_set_variant(0)
+    return out
+
+
+CONV_LN_WIDE_CASES = [(3, 1101, 3, 2), (2, 1046, 2, 2), (2, 1047, 2, 2), (2, 513, 3, 2)]   # B, T_in, k, s
+
+
+def check_conv_ln_block_wide():
+    """check_conv_ln_block (conv with bias -> LayerNorm over channels -> GELU, the LayerNorm's backward writing straight into
+    the conv's zero-padded gradient layout) at sizes the tile kernels take, under every kernel variant, into poisoned
+    allocations: more rows than one block of the LayerNorm grid handles, and the hand-off of the padded gradient with
+    ragged 256-row tiles behind it."""
+    out = [_poison_reaches_empty(64 << 20)]
+    C, dtype = CONV_WIDE_C, torch.bfloat16
+    saved = ops.LN_SEG_OK
+    try:
+        for (B, T_in, k, s_) in CONV_LN_WIDE_CASES:
+            tag0 = f"conv+LN block wide B={B} T={T_in} k={k} s={s_}"
+            out.append((f"{tag0}: launches below the tile kernels' shapes", conv_shape_guard(T_in, ((k, s_),), C), 0.0))
+            x = q(gen(B, T_in, C, seed=1), dtype)
+            W = q(gen(C, C, k, seed=2, scale=1.0 / math.sqrt(C * k)), dtype)
+            cb = q(0.1 * gen(C, seed=3), dtype)
+            g, b = q(1 + 0.1 * gen(C, seed=4), dtype), q(0.1 * gen(C, seed=5), dtype)
+            ts = [t.double().clone().requires_grad_(True) for t in (x, W, cb, g, b)]
+            yr = TF.gelu(TF.layer_norm(TF.conv1d(ts[0].transpose(1, 2), ts[1], ts[2], stride=s_).transpose(1, 2), (C,), ts[3], ts[4], 1e-5))
+            dy = q(gen(*yr.shape, seed=6), dtype)
+            gr = torch.autograd.grad(yr, ts, dy.double())
+            rows = _edge_rows(T_in)
+            tail = unused_trailing_frames(T_in, k, s_)
+            nbytes = 8 * x.numel() * 2 + (16 << 20)
+            for v in CONV_WIDE_VARIANTS:
+                ops.gemm_set_variant(v)
+                res = {}
+                for seg in (True, False):
+                    ops.LN_SEG_OK = seg
+                    td = [t.to(dtype).to(DEV).requires_grad_(True) for t in (x, W, cb, g, b)]
+                    dyd = dy.to(dtype).to(DEV)
+                    _poison(nbytes)
+                    u = F.ConvStackFn.apply(td[0], ((k, s_),), False, td[1], td[2])
+                    y, _ = F.layer_norm(u, td[3], td[4], 1e-5, act=1, grad_pad=F.conv_grad_pad(T_in, k, s_))
+                    _poison(nbytes)
+                    res[seg] = (y,) + torch.autograd.grad(y, td, dyd)
+                tag = f"{tag0} variant {v}"
+                out.append((tag + " y", err(res[True][0], yr), TOLBF))
+                for nm, a, r in zip(("dx", "dW", "dbias", "dgamma", "dbeta"), res[True][1:], gr):
+                    out.append((tag + " " + nm, err(a, r), TOLBF))
+                out.append((tag + " dx boundary rows", err(res[True][1][:, rows], gr[0][:, rows]), TOLBF))
+                if tail > 0:
+                    out.append((tag + " dx unused trailing frame == 0", float((res[True][1][:, -tail:] != 0).sum().item()), 0.0))
+                for nm, a, c in zip(("y", "dx", "dW", "dbias", "dgamma", "dbeta"), res[True], res[False]):
+                    out.append((tag + " " + nm + " == the padded-copy path", 0.0 if torch.equal(a, c) else 1.0, 0.0))
+    finally:
+        ops.LN_SEG_OK = saved
+        ops.gemm_set_variant(0)
     return out
 
 
@@ -1638,7 +1923,7 @@ def check_activations():
 
 GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
-    "convstack": check_convstack, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
+    "conv_ln_block_wide": check_conv_ln_block_wide, "convstack": check_convstack, "convstack_wide": check_convstack_wide, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
     "linear_ffn": check_linear_ffn, "activations": check_activations, "loss": check_loss, "adam": check_adam, "dropout_exact": check_dropout_exact,
     "gumbel_vq": check_gumbel_vq, "sampled_negatives": check_sampled_negatives,
 }
