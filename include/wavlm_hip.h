@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 28
+#define WAVLM_HIP_ABI_VERSION 29
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -564,7 +564,9 @@ int wavlm_kmeans_update(float* C, float* weights, const float* sums, const int32
  *                          are HOST arrays of n_states <= 32 device pointers / element strides (unit channel stride; the
  *                          tensors are read where extract_features left them); `weights` fp32 [n_states] on the device (the
  *                          softmax already applied).  Every state is read once for T <= 1024 (the mixed slab stays in LDS);
- *                          later frames are mixed three times.  Rows [-pad, 0) and [T, T + pad) of every utterance of `out`
+ *                          later frames are mixed three times.  n_states == 1 (ABI 29: the log-mel features of csrc/fbank.hip,
+ *                          fp32 in, the head's dtype out): sums are taken about the column's first frame, so a constant
+ *                          column normalises to exactly 0; several states are summed as before, bit for bit.  Rows [-pad, 0) and [T, T + pad) of every utterance of `out`
  *                          are written as zeros (the k = 5 convolution's padding): `out` points at row 0.
  *   wavlm_spk_rowact       ecapa_tdnn.py:63-64 / :282 / :154: y = act(x) * scale[c] + shift[c], act 0 = ReLU, 1 = tanh,
  *                          2 = none; scale / shift fp32 [C] (BatchNorm folded: w / sqrt(var + eps), b - mean * scale) or
@@ -684,6 +686,31 @@ int64_t wavlm_mfcc_frames(int64_t len, int32_t W, int32_t S);
 int wavlm_mfcc_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
                     int32_t S, int32_t P, const float* window, const float* twiddle, const int32_t* mel_idx, const float* mel_w,
                     int32_t n_mel_w, const float* dct, float* y, int64_t y_stride, int64_t Mmax, int32_t ncol, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Log-mel filter bank (ABI 29, csrc/fbank.hip): the front end of the ECAPA-TDNN baseline without an upstream,
+ * downstreams/speaker_verification/models/ecapa_tdnn.py:179-182, 253, 257 (feat_type='fbank'):
+ * torchaudio.transforms.MelSpectrogram(sample_rate=sr, n_fft=P, win_length=W, hop_length=S, f_min=0, f_max=sr // 2, pad=0,
+ * n_mels=M) at its defaults otherwise (periodic Hann, power 2, centre, reflect, one-sided, HTK scale, no norm), + 1e-6, log.
+ * The speaker model's geometry is W = 400, S = 160, P = 512, M = 40 at 16 kHz.
+ *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype 0 / 2; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
+ *   lengths  NULL or B sample counts (clamped to [0, L]): a row ends there and is reflected at its own end
+ *   window [W], twiddle [P][2] = (cos, -sin)(2 pi t / P), mel_idx [M][3] = (first bin, count, offset into mel_w), mel_w
+ *   [n_mel_w <= P]: filter m = sum_i mel_w[offset + i] * power[first + i] over bins < P / 2 -- computed by the host in float64
+ *   and rounded to fp32 once (unispeech_amd/fbank.py); out-of-range mel_idx entries are clamped, never followed
+ *   y        fp32 [B, Tmax, M] channel-last, row stride y_stride >= Tmax * M in elements; Tmax >= wavlm_fbank_frames(L, S, P);
+ *            y[b, t, m] = log(sum_k fb[k, m] |rfft_P(frame t)|^2[k] + 1e-6); frames at or beyond a row's own count are
+ *            written as zero
+ * One launch, nothing staged in HBM.  Fixed arithmetic order: a row's features are bitwise the same wherever the row sits in the
+ * batch.  wavlm_fbank_supported (host): 1 if P is a power of two in [64, 512], P / 2 < W <= P, 1 <= S <= W, 1 <= M <= 128 and
+ * the tile fits 80 KiB of LDS; wavlm_fbank_rows returns -1 otherwise.  wavlm_fbank_frames (host): 0 for len <= P / 2 (the
+ * reflection needs more samples), else 1 + len / S.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_fbank_supported(int32_t W, int32_t S, int32_t P, int32_t M);
+int64_t wavlm_fbank_frames(int64_t len, int32_t S, int32_t P);
+int wavlm_fbank_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
+                     int32_t S, int32_t P, int32_t M, const float* window, const float* twiddle, const int32_t* mel_idx,
+                     const float* mel_w, int32_t n_mel_w, float* y, int64_t y_stride, int64_t Tmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

@@ -10,7 +10,8 @@
 // One launch.  A workgroup of 4 waves owns MF_FT = 56 output frames of one row and computes the cepstra of MF_NF = 64 frames:
 // its own and 4 on either side, which is what the second-order delta reaches, so no cepstrum, spectrum or log-mel value ever
 // goes to HBM and nothing is exchanged between workgroups.  The (MF_NF - 1) S + W samples of the tile go to LDS once (int16
-// scaled by 1 / 32768, samples outside [0, len) as zero).  A wave takes one frame at a time: the real P-point transform is the
+// scaled by 1 / 32768, samples outside [0, len) as zero).  A wave takes one frame at a time (fft_wave.hpp, shared with
+// fbank.hip, holds the transform): the real P-point transform is the
 // complex P / 2-point transform of z[n] = y[2n] + i y[2n + 1] -- Stockham radix-4 passes (one radix-2 pass when log2(P / 2) is
 // odd) between two wave-private LDS buffers, one butterfly per lane and pass at P = 512 -- and the split
 //   X[k] = (Z[k] + conj Z[H - k]) / 2 + w_P^k (Z[k] - conj Z[H - k]) / 2i,      H = P / 2, k < H
@@ -19,6 +20,7 @@
 // Arithmetic order is fixed and depends on nothing but the row's samples and the frame's index in the row (tiles start at frame
 // 0 of every row): a row's features are bit-identical wherever the row sits in the batch and whatever the other rows hold.
 #include "common.hpp"
+#include "fft_wave.hpp"
 #include "../../include/wavlm_hip.h"
 
 #define MF_NT 256
@@ -62,47 +64,8 @@ __device__ __forceinline__ float mf_load(const void* x, long i, int dt) {
   return dt == MF_I16 ? (float)((const short*)x)[i] * (1.0f / 32768.0f) : ((const float*)x)[i];
 }
 
-// Butterflies are evaluated in fp64 registers on fp32 operands (samples, twiddles) and stored to LDS as fp32: a value is rounded
-// once per pass instead of once per multiply and add, which is what keeps the transform's error near that of a transform
-// evaluated exactly and rounded at the end (numpy's single-precision rfft, the tests' fp32 oracle, behaves like that)
-struct mf_c64 { double x, y; };
-__device__ __forceinline__ mf_c64 mf_wide(float2 a) { return {(double)a.x, (double)a.y}; }
-__device__ __forceinline__ float2 mf_narrow(double x, double y) { return make_float2((float)x, (float)y); }
-__device__ __forceinline__ mf_c64 mf_cmul(mf_c64 a, float2 w) {
-  return {a.x * (double)w.x - a.y * (double)w.y, a.x * (double)w.y + a.y * (double)w.x};
-}
-
 // sum_k k v[k + 2] / 10 as differences of the mirrored pairs: a constant stretch (digital silence at the floor) gives exactly 0
 __device__ __forceinline__ float mf_delta(const float* v) { return ((v[3] - v[1]) + 2.0f * (v[4] - v[0])) / 10.0f; }
-
-// one Stockham pass of radix R over H points: Ns = product of the radices before it; twiddles w_H^t = tw[2 t]
-template <int R>
-__device__ __forceinline__ void mf_pass(const float2* __restrict__ in, float2* __restrict__ out, const float2* __restrict__ tw,
-                                        int H, int Ns, int lane) {
-  const int T = H / R;
-  for (int j = lane; j < T; j += 64) {
-    const int k = j & (Ns - 1);
-    const int step = 2 * k * (H / (Ns * R));
-    mf_c64 v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) v[r] = mf_wide(in[j + r * T]);
-#pragma unroll
-    for (int r = 1; r < R; ++r) v[r] = mf_cmul(v[r], tw[r * step]);
-    float2* o = out + (j - k) * R + k;
-    if (R == 2) {
-      o[0] = mf_narrow(v[0].x + v[1].x, v[0].y + v[1].y);
-      o[Ns] = mf_narrow(v[0].x - v[1].x, v[0].y - v[1].y);
-    } else {
-      const mf_c64 a0 = {v[0].x + v[2].x, v[0].y + v[2].y}, a1 = {v[0].x - v[2].x, v[0].y - v[2].y};
-      const mf_c64 a2 = {v[1].x + v[3].x, v[1].y + v[3].y};
-      const mf_c64 a3 = {v[1].y - v[3].y, v[3].x - v[1].x};                     // -i (v1 - v3)
-      o[0] = mf_narrow(a0.x + a2.x, a0.y + a2.y);
-      o[Ns] = mf_narrow(a1.x + a3.x, a1.y + a3.y);
-      o[2 * Ns] = mf_narrow(a0.x - a2.x, a0.y - a2.y);
-      o[3 * Ns] = mf_narrow(a1.x - a3.x, a1.y - a3.y);
-    }
-  }
-}
 
 __global__ __launch_bounds__(MF_NT) void mfcc_kernel(const void* __restrict__ x, int x_dt, long x_stride, long L,
     const int* __restrict__ lengths, int W, int S, int P, const float* __restrict__ window, const float* __restrict__ twiddle,
@@ -178,31 +141,12 @@ __global__ __launch_bounds__(MF_NT) void mfcc_kernel(const void* __restrict__ x,
       }
       bufA[h] = z;
     }
-    __syncthreads();
     float2* src = bufA;
     float2* dst = bufB;
-    int Ns = 1;
-    for (; Ns * 4 <= H; Ns *= 4) {
-      mf_pass<4>(src, dst, s_tw, H, Ns, lane);
-      __syncthreads();
-      float2* t = src; src = dst; dst = t;
-    }
-    if (Ns < H) {
-      mf_pass<2>(src, dst, s_tw, H, Ns, lane);
-      __syncthreads();
-      float2* t = src; src = dst; dst = t;
-    }
+    mf_transform(src, dst, s_tw, H, lane);
     // power spectrum of the real transform, bins 0 .. H - 1 (the Nyquist bin has weight zero)
     float* pw = (float*)dst;
-    for (int k = lane; k < H; k += 64) {
-      const mf_c64 zk = mf_wide(src[k]), zn = mf_wide(src[(H - k) & (H - 1)]);
-      const mf_c64 ev = {0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y)};             // (Z[k] + conj Z[H - k]) / 2
-      const mf_c64 od = {0.5 * (zk.y + zn.y), -0.5 * (zk.x - zn.x)};            // (Z[k] - conj Z[H - k]) / 2i
-      const mf_c64 t = mf_cmul(od, s_tw[k]);
-      const double re = ev.x + t.x, im = ev.y + t.y;
-      pw[k] = (float)(re * re + im * im);
-    }
-    __syncthreads();
+    mf_power(src, pw, s_tw, H, lane);
     float* lg = (float*)src;
     if (lane < MF_NMEL) {
       const int first = s_meli[3 * lane], count = s_meli[3 * lane + 1], off = s_meli[3 * lane + 2];

@@ -7,6 +7,8 @@
 //                          (utterance, 32-channel slab) over all of T' and keeps the mixed slab in LDS as fp32: every state
 //                          is read ONCE, the result written once.  Frames beyond the 1024 the slab holds (20.5 s) are mixed
 //                          again in the variance and the write pass (three reads of those frames only).
+//                          A single state (the fbank front end's log-mel features, unispeech_amd/fbank.py) is summed about
+//                          its first frame: a constant column normalises to exactly zero.
 //   wavlm_spk_rowact       y = act(x) * scale + shift per channel (ReLU then BatchNorm's affine: Conv1dReluBn, :63-64; plain
 //                          ReLU, :282; tanh, :154), absent frames zeroed, and optionally the time mean of y over the valid
 //                          frames (SE_Connect's x.mean(dim=2), :78) from the same pass: a workgroup owns (utterance, 64
@@ -108,23 +110,27 @@ __global__ __launch_bounds__(MIX_NT) void spk_mix_norm_kernel(SpkStates S, int n
   if (tid < n) ws[tid] = w[tid];
   __syncthreads();
 
-  float sum[V], m[V];
+  // One state (a feature front end: log-mel columns) is summed about the column's first frame, so a constant column -- digital
+  // silence, an empty mel filter -- has mean = its value and normalises to exactly 0.  Several states: the pivot is 0 and the
+  // sums are the plain ones, bit for bit.
+  float sum[V], m[V], piv[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) sum[j] = 0.f;
+  for (int j = 0; j < V; ++j) { sum[j] = 0.f; piv[j] = 0.f; }
+  if (n == 1 && cin && len > 0) mix_at<V>(S, n, dt, ws, b, 0, c, add, piv);
   if (cin)
     for (int t = ph; t < len; t += PH) {
       mix_at<V>(S, n, dt, ws, b, t, c, add, m);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         if (t < slab_T) slab[t * MIX_CS + cl + j] = m[j];
-        sum[j] += m[j];
+        sum[j] += m[j] - piv[j];
       }
     }
   mix_reduce<V, PH>(red, cl, ph, sum);
   const float inv_n = len > 0 ? 1.f / (float)len : 0.f;
   float mean[V], sq[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) { mean[j] = sum[j] * inv_n; sq[j] = 0.f; }
+  for (int j = 0; j < V; ++j) { mean[j] = piv[j] + sum[j] * inv_n; sq[j] = 0.f; }
   if (cin)
     for (int t = ph; t < len; t += PH) {
       if (t < slab_T) {

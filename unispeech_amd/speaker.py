@@ -10,6 +10,9 @@ The inference path of the reference's downstreams/speaker_verification: `models/
     distinct waveform length; `forward_states(states, lengths)` -- the head alone; `forward(wavs)` -- both.
   * `score(emb1, emb2)` -- cosine; `python -m unispeech_amd.speaker embed|verify UPSTREAM.pt HEAD.pt a.wav [b.wav]` (a file
     that is not at 16 kHz is resampled to it on the device, unispeech_amd/resample.py, as verification.py:46-49 does).
+  * `ECAPA_TDNN(feat_dim=40, feat_type="fbank")` -- the reference's baseline without an upstream (verification.py's
+    `ecapa_tdnn`): waveform -> log-mel filter bank on the device (unispeech_amd/fbank.py, one launch) -> the same head, layer 1
+    a GEMM with K = 5 * 40; `... embed|verify --fbank HEAD.pt a.wav [b.wav]` on the command line.
 Inference only (eval mode, BatchNorm running statistics, no gradients).  No CPU path and no eager fall-back for the kernels:
 every tensor-sized step of the head is a libwavlm_hip.so entry point.  What torch does here is small and parameter- or
 waveform-sized: the softmax of feature_weight, folding the BatchNorms and packing the Res2 weights (about 25 launches per call,
@@ -25,7 +28,7 @@ from . import _lib
 from . import functional as F
 from . import ops
 
-__all__ = ["ECAPA_TDNN", "ECAPA_TDNN_SMALL", "score", "frame_count", "load_pair"]
+__all__ = ["ECAPA_TDNN", "ECAPA_TDNN_SMALL", "score", "frame_count", "load_pair", "load_fbank"]
 
 RES2_WIDTH = 64   # csrc/spkhead.hip: channels per Res2 split
 RES2_SCALE = 8
@@ -79,6 +82,20 @@ class Upstream(nn.Module):
     def __init__(self, model):
         super().__init__()
         self.model = model
+
+
+class MelBuffers(nn.Module):
+    """the state-dict entries of the reference's `feature_extract` in fbank mode, a torchaudio MelSpectrogram:
+    `spectrogram.window` [W] and `mel_scale.fb` [n_fft / 2 + 1, n_mels], so that key sets agree.  They hold what torchaudio
+    builds (fbank.tables / fbank.mel_bank rounded to fp32); the kernel reads its own by-filter tables, never these."""
+
+    def __init__(self, sr, n_fft, win_length, n_mels):
+        super().__init__()
+        from . import fbank as FB
+        self.spectrogram, self.mel_scale = nn.Module(), nn.Module()
+        t = FB.tables(sr, n_fft, win_length, n_mels)
+        self.spectrogram.register_buffer("window", torch.from_numpy(t["window"].astype("float32")))
+        self.mel_scale.register_buffer("fb", torch.from_numpy(FB.mel_bank(sr, n_fft, n_mels).astype("float32")))
 
 
 def frame_count(n_samples, conv_feature_layers="[(512,10,5)] + [(512,3,2)] * 4 + [(512,2,2)] * 2"):
@@ -151,10 +168,13 @@ class UpstreamStates:
 
 
 class ECAPA_TDNN(UpstreamStates, nn.Module):
-    """ecapa_tdnn.py:163-286 with feat_type = an upstream model and feature_selection="hidden_states".
+    """ecapa_tdnn.py:163-286 with feat_type = an upstream model and feature_selection="hidden_states", or feat_type="fbank".
 
     feat_dim: width D of the states; upstream: a unispeech_amd.wavlm.WavLM (its keys appear under feature_extract.model.*)
-    or None for the head alone, in which case num_states (L + 1) must be given."""
+    or None for the head alone, in which case num_states (L + 1) must be given.
+    feat_type="fbank": feat_dim is the number of mel filters (40 in verification.py); no upstream, no states and no
+    feature_weight -- forward(wavs) computes the log-mel features itself (unispeech_amd/fbank.py)."""
+    FBANK_N_FFT = 512   # ecapa_tdnn.py:180
 
     def __init__(self, feat_dim, channels=512, emb_dim=192, upstream=None, num_states=None, global_context_att=False,
                  feat_type="upstream", sr=16000, feature_selection="hidden_states", update_extract=False):
@@ -162,9 +182,18 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         if global_context_att:
             raise NotImplementedError("global_context_att=True (context mean / std concatenated in AttentiveStatsPool) is "
                                       "not built")
-        if feat_type in ("fbank", "mfcc"):
-            raise NotImplementedError("feat_type=%r: the torchaudio fbank / mfcc front ends are not built; the head runs on "
-                                      "an upstream model's hidden states" % feat_type)
+        if feat_type == "mfcc":
+            raise NotImplementedError("feat_type=%r: the torchaudio mfcc front end is not built; the head runs on an upstream "
+                                      "model's hidden states or on feat_type='fbank'" % feat_type)
+        self.fbank = feat_type == "fbank"
+        if self.fbank:
+            from .fbank import MAX_MELS
+            if not 1 <= int(feat_dim) <= MAX_MELS:
+                raise NotImplementedError("feat_type='fbank' with feat_dim=%d: the fbank kernel takes 1 to %d mel filters "
+                                          "(verification.py's ecapa_tdnn uses 40)" % (feat_dim, MAX_MELS))
+            if upstream is not None or num_states not in (None, 1):
+                raise ValueError("feat_type='fbank' takes neither an upstream nor num_states: the features are computed "
+                                 "from the waveform")
         if update_extract:
             raise NotImplementedError("update_extract=True (fine-tuning the upstream through the head) is not built: "
                                       "inference only")
@@ -177,7 +206,10 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
             raise NotImplementedError("channels=%d: the Res2 kernel is built for 8 splits of 64 channels (channels=512)"
                                       % channels)
         self.feat_dim, self.sr = int(feat_dim), sr
-        if upstream is not None:
+        if self.fbank:
+            self.feature_extract = MelBuffers(sr, self.FBANK_N_FFT, int(sr * 0.025), self.feat_dim)
+            num_states = 1
+        elif upstream is not None:
             self.feature_extract = Upstream(upstream)
             n = len(upstream.encoder.layers) + 1
             if num_states is not None and num_states != n:
@@ -190,7 +222,8 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         elif num_states is None:
             raise ValueError("num_states is required without an upstream")
         self.feat_num = int(num_states)
-        self.feature_weight = nn.Parameter(torch.zeros(self.feat_num))
+        if not self.fbank:   # ecapa_tdnn.py:203-205: the reference has none in fbank mode either
+            self.feature_weight = nn.Parameter(torch.zeros(self.feat_num))
         self.instance_norm = nn.InstanceNorm1d(feat_dim)
         self.channels = [channels] * 4 + [1536]
         self.layer1 = Conv1dReluBn(feat_dim, channels, kernel_size=5)
@@ -208,7 +241,10 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         return [t for n, t in list(self.named_parameters()) + list(self.named_buffers()) if not n.startswith(up)]
 
     def _build_images(self):
-        im = {"w": torch.softmax(self.feature_weight.float(), dim=-1).contiguous()}
+        if self.fbank:
+            im = {"w": torch.ones(1, dtype=torch.float32, device=self.layer1.conv.weight.device)}
+        else:
+            im = {"w": torch.softmax(self.feature_weight.float(), dim=-1).contiguous()}
         D = self.feat_dim
         im["l1_w"] = self.layer1.conv.weight.permute(0, 2, 1).reshape(-1, 5 * D).contiguous()  # [out, tap * D + in]
         blocks = [getattr(self, n) for n in ("layer2", "layer3", "layer4")]
@@ -266,6 +302,8 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         (UpstreamExpert.forward, utils.py:59-60).  Unequal lengths: one upstream call per distinct length (what one
         verification.py call per file computes); absent frames are zero."""
         self._inference_only()
+        if self.fbank:
+            raise ValueError("an fbank model has no upstream and no hidden states: use forward or fbank_features")
         if not hasattr(self, "feature_extract"):
             raise ValueError("this head was built without an upstream: use forward_states")
         m = self.feature_extract.model
@@ -293,6 +331,8 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         lengths: frames per utterance (absent frames never reach an output).  Returns embeddings [B, emb_dim].
         intermediates (a dict, optional) receives `normed`, `out2_mean`, `out4_mean`, `pooled` for the tests."""
         self._inference_only()
+        if self.fbank:
+            raise ValueError("an fbank model has no hidden states: use forward")
         if isinstance(states, torch.Tensor):
             states = list(states.unbind(0))
         states = [s if s.stride(-1) == 1 and s.stride(1) >= s.shape[2] else s.contiguous() for s in states]
@@ -317,8 +357,10 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         with torch.no_grad():
             return self._head(states, len_t, B, T, D, dev, dtype, dt, intermediates)
 
-    def _head(self, states, len_t, B, T, D, dev, dtype, dt, inter):
+    def _head(self, states, len_t, B, T, D, dev, dtype, dt, inter, sdt=None):
+        """dtype / dt: the head's; sdt: the states' dtype code when it differs (fp32 log-mel features into a bf16 head)"""
         L = _lib.lib()
+        sdt = dt if sdt is None else sdt
         st = ops.stream
         im = self._images()
         n = len(states)
@@ -332,8 +374,8 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in states])
         sb = (C.c_int64 * n)(*[s.stride(0) for s in states])
         stt = (C.c_int64 * n)(*[s.stride(1) for s in states])
-        _lib.check(L.wavlm_spk_mix_norm(ptrs, sb, stt, n, dt, _p(im["w"]), lp, B, T, D, ops.ptr(xp, 2 * D), dt, (T + 4) * D, D, 2,
-                                        1e-6, self.instance_norm.eps, st()), "wavlm_spk_mix_norm")
+        _lib.check(L.wavlm_spk_mix_norm(ptrs, sb, stt, n, sdt, _p(im["w"]), lp, B, T, D, ops.ptr(xp, 2 * D), dt, (T + 4) * D, D, 2,
+                                        0.0 if self.fbank else 1e-6, self.instance_norm.eps, st()), "wavlm_spk_mix_norm")
         if inter is not None:
             inter["normed"] = xp[:, 2:T + 2]
 
@@ -396,10 +438,43 @@ class ECAPA_TDNN(UpstreamStates, nn.Module):
         ops.gemm(pooled, self.linear.weight, emb, B, E, 2 * cc, lda=2 * cc, ldb=2 * cc, ldc=E, bias=self.linear.bias)
         return emb
 
-    def forward(self, wavs):
+    # -- fbank front end ---------------------------------------------------------------------------------------------------
+    def fbank_features(self, wavs):
+        """list of 1-D 16 kHz mono waveforms (float, or int16 PCM) or [B, T] -> (log-mel features fp32 [B, Tmax, feat_dim],
+        frames per utterance): ecapa_tdnn.py:253 (MelSpectrogram + 1e-6) and :257 (log), one launch for the whole list"""
+        from . import fbank as FB
+        if not self.fbank:
+            raise ValueError("this model runs on an upstream's hidden states, not on fbank features")
+        dev = self.layer1.conv.weight.device
+        wavs = [w.to(device=dev, dtype=torch.int16 if w.dtype == torch.int16 else torch.float32) for w in self._wav_list(wavs)]
+        if len({w.dtype for w in wavs}) != 1:
+            raise ValueError("waveforms of one call share a dtype (float or int16 PCM)")
+        W, S, P = FB.geometry(self.sr, self.FBANK_N_FFT)
+        frames = [FB.frames(len(w), S, P) for w in wavs]
+        if min(frames) < 1:
+            raise ValueError("a waveform of %d samples: the reflection at its ends needs more than %d"
+                             % (min(len(w) for w in wavs), P // 2))
+        x = torch.stack(wavs) if len({len(w) for w in wavs}) == 1 else wavs
+        return FB.fbank(x, sr=self.sr, n_mels=self.feat_dim, n_fft=P, win_length=W, hop_length=S), frames
+
+    def _forward_fbank(self, wavs, intermediates=None):
+        self._inference_only()
+        with torch.no_grad():
+            feats, frames = self.fbank_features(wavs)
+            B, T, D = feats.shape
+            w0 = self.layer1.conv.weight
+            len_t = None
+            if min(frames) != T:
+                len_t = torch.tensor(frames, dtype=torch.int32).to(w0.device)
+            # the 1e-6 is inside the log already: one fp32 "state", weight 1, add 0, normed into the head's dtype
+            return self._head([feats], len_t, B, T, D, w0.device, w0.dtype, ops.dt(w0), intermediates, sdt=_lib.F32)
+
+    def forward(self, wavs, intermediates=None):
         """list of 1-D 16 kHz mono waveforms or [B, T] -> embeddings [B, emb_dim] (ecapa_tdnn.py:273-286)"""
+        if self.fbank:
+            return self._forward_fbank(wavs, intermediates)
         states, frames = self.hidden_states(wavs)
-        return self.forward_states(states, frames)
+        return self.forward_states(states, frames, intermediates)
 
 
 def ECAPA_TDNN_SMALL(feat_dim, emb_dim=256, **kwargs):
@@ -452,25 +527,48 @@ def load_pair(upstream_path, head_path, emb_dim=256):
     return model.cuda().eval()
 
 
+def load_fbank(head_path, emb_dim=256, feat_dim=40):
+    """head checkpoint {'model': state dict} (the reference's released ECAPA-TDNN file) -> ECAPA_TDNN_SMALL(feat_dim,
+    feat_type='fbank') on the device, eval mode; loaded with strict=False as verification.py:30-33 does"""
+    model = ECAPA_TDNN_SMALL(feat_dim, emb_dim=emb_dim, feat_type="fbank")
+    head = torch.load(head_path, map_location="cpu", weights_only=False)
+    head = head["model"] if isinstance(head, dict) and "model" in head else head
+    # the front end's own tables stay: the kernel is built from them, not from the file's
+    model.load_state_dict({k: v for k, v in head.items() if not k.startswith("feature_extract.")}, strict=False)
+    return model.cuda().eval()
+
+
 def parse_args(argv=None):
+    """embed|verify UPSTREAM.pt HEAD.pt wavs...; with --fbank (verification.py's ecapa_tdnn: no upstream) HEAD.pt wavs..."""
     import argparse
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    fb = "--fbank" in argv
     ap = argparse.ArgumentParser(prog="python -m unispeech_amd.speaker")
     sub = ap.add_subparsers(dest="cmd", required=True)
     p = sub.add_parser("embed", help="print the embedding of each wav file")
-    p.add_argument("upstream"); p.add_argument("head"); p.add_argument("wavs", nargs="+")
+    if not fb:
+        p.add_argument("upstream")
+    p.add_argument("head"); p.add_argument("wavs", nargs="+")
     p = sub.add_parser("verify", help="verification.py: cosine score of two wav files")
-    p.add_argument("upstream"); p.add_argument("head"); p.add_argument("wav1"); p.add_argument("wav2")
+    if not fb:
+        p.add_argument("upstream")
+    p.add_argument("head"); p.add_argument("wav1"); p.add_argument("wav2")
     for q in sub.choices.values():
         q.add_argument("--emb_dim", default=256, type=int)
         q.add_argument("--bf16", action="store_true", help="run upstream and head in bf16")
-    return ap.parse_args(argv)
+        q.add_argument("--fbank", action="store_true", help="the ECAPA-TDNN baseline on 40 log-mel filters: no upstream argument")
+    a = ap.parse_args(argv)
+    if fb:
+        a.upstream = None
+    return a
 
 
 def main(argv=None):
     a = parse_args(argv)
     paths = a.wavs if a.cmd == "embed" else [a.wav1, a.wav2]
     wavs = [read_wav(p) for p in paths]
-    model = load_pair(a.upstream, a.head, a.emb_dim)
+    model = load_fbank(a.head, a.emb_dim) if a.fbank else load_pair(a.upstream, a.head, a.emb_dim)
     if a.bf16:
         model = model.to(torch.bfloat16)
     with torch.no_grad():
