@@ -4,6 +4,20 @@ tools/gpu_report.py (crash-isolated report).  Every check returns a list of (nam
 
 Error metric: max |a - b| / max(|b|_max, tiny) -- "relative to the tensor scale" -- unless noted.
 Tolerances: fp32 mode 1e-4 (BASELINE.json north_star) except long fp32 reductions (2e-4); bf16 mode 2e-2.
+
+The row kernels (rowops.hip, optim.hip) are grid-stride kernels with a grid cap, and four groups run them where a wave or a
+thread takes several items, against fp64 torch on the device.  Their shapes rest on the launch geometry -- 4 rows per block,
+LayerNorm caps of 1024 blocks (forward: full-width kernels, and every forward with dropout), 512 (backward, LN_BWD_BLOCKS) and
+8192 (general forward without dropout), rows / 128 and rows / 256 above 131 072 rows, CS_BLOCKS = 512 for colsum -- so a retuned
+cap moves the shape named beside it:
+  layernorm_rows         8195 rows (= 2 * 4096 + 3 = 4 * 2048 + 3: 2-3 rows per forward wave, 4-5 per backward wave, ragged last
+                         sweeps), 1 / 5 / 8192 rows, 32 773 rows (general forward past 4 * 8192), 262 149 rows (past the cap change)
+  layernorm_dropout_ref  8195 rows: forward (1024 blocks) and backward (512) regenerate one mask with different row assignments
+  colsum_rows            799 / 1027 / 1795 / 2048 / 8195 rows = 200 / 257 / 449 / 512 / 512 partial rows (the finish kernel's unrolled
+                         loop needs more than 192), the last one strided over CS_BLOCKS
+  flat_strided           n just past 16384 x 256 (adam_step), 8192 x 256 (axpby, scale_dev; x 8 for dropout, dropout_add),
+                         1024 x 4096 (sumsq), 4096 x 256 x 8 (select_rows, gather_rows)
+tests/test_kernels_gpu.py runs the two LayerNorm groups once more in a fresh process under WAVLM_LN_FULL=0.
 """
 import math
 import sys
@@ -1921,21 +1935,544 @@ def check_activations():
     return out
 
 
+# ------------------------------------------------------------------ row kernels where a wave walks several rows
+# Row counts below rest on the launch geometry of rowops.hip / optim.hip: 4 rows per block (one per wave); LayerNorm grid caps
+# 1024 (forward, full-width kernels and every forward with dropout), 512 (backward, LN_BWD_BLOCKS), 8192 (general forward without
+# dropout), above 131 072 rows: rows / 128 (forward) and rows / 256 (backward); CS_BLOCKS = 512 partial rows of colsum.
+LN_ROWS = 8195            # = 2 * 4096 + 3 = 4 * 2048 + 3: forward waves take 2 or 3 rows, backward waves 4 or 5, both last sweeps ragged
+LN_ROWS_GENERAL = 32773   # = 32 768 + 5: the general forward without dropout (cap 8192) gives some waves a second row
+LN_ROWS_BIG = 262149      # = 2 * 131 072 + 5: caps 2048 (forward) and 1024 (backward)
+LN_WIDTHS = (512, 768, 1024)
+TOL32_SUM = 2e-4          # long fp32 reductions (module docstring)
+
+
+def ln_full_enabled():
+    """rowops.hip's reading of WAVLM_LN_FULL (first character '0': the general kernels at every width)"""
+    import os
+    return os.environ.get("WAVLM_LN_FULL", "1")[:1] != "0"
+
+
+def leaves_no_footprint(fn):
+    """run a group and put ops' grow-only workspaces back as they were, then release the cache: a workspace grown while large
+    freed blocks are cached pins such a block with stale data around it, and the poisoned allocations of the conv checks that
+    run later in the same process (_poison_reaches_empty) would be handed that memory instead of the NaN-filled block"""
+    import functools
+
+    @functools.wraps(fn)
+    def run():
+        saved = dict(ops._WS)
+        try:
+            return fn()
+        finally:
+            torch.cuda.synchronize()
+            ops._WS.clear()
+            ops._WS.update(saved)
+            _LN_RAW.clear()
+            torch.cuda.empty_cache()
+    return run
+
+
+def errd(a, b):
+    """err()'s metric for device tensors, evaluated where they live (one scalar crosses to the host instead of both tensors;
+    a NaN or an infinity anywhere in `a` gives inf, as there)"""
+    if a.shape != b.shape:
+        return float("inf")
+    if b.numel() == 0:
+        return 0.0
+    a, b = a.detach().double(), b.detach().double()
+    v = ((a - b).abs().max() / b.abs().max().clamp_min(1e-12)).item()
+    return v if math.isfinite(v) else float("inf")
+
+
+def dgen(*shape, seed, scale=1.0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return torch.randn(*shape, generator=g, device=DEV) * scale
+
+
+def refused(fn):
+    """0.0 iff fn() ends in check()'s invalid-argument error"""
+    from unispeech_amd._lib import WavlmHipError
+    try:
+        fn()
+    except WavlmHipError as e:
+        return 0.0 if "invalid argument" in str(e) else 1.0
+    return 1.0
+
+
+def same_bits(a, b):
+    a, b = a.contiguous(), b.contiguous()
+    return 0.0 if a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8)) else 1.0
+
+
+_LN_RAW = {}
+
+
+def ln_inputs(rows, D, dtype, pdtype):
+    """fp32 device tensors rounded through the tested dtypes (x, r, dy, extra through dtype; g, b through pdtype): the raw
+    draws are made once per (rows, D) and shared by every case of a group"""
+    raw = _LN_RAW.get((rows, D))
+    if raw is None:
+        raw = dict(x=dgen(rows, D, seed=1), r=dgen(rows, D, seed=2), dy=dgen(rows, D, seed=5), extra=dgen(rows, D, seed=23),
+                   g=1 + 0.1 * dgen(D, seed=3), b=0.1 * dgen(D, seed=4))
+        _LN_RAW[(rows, D)] = raw
+    return {k: q(v, pdtype if k in ("g", "b") else dtype) for k, v in raw.items()}
+
+
+def ln_ref(I, dtype, act, res, m_in=None, m_out=None, eps=1e-5):
+    """y = m_out * act(LN(x + m_in * r)) in fp64 on the device and its gradients for the cotangent dy through autograd; the
+    pre-norm sum takes the bf16 rounding of the stored tensor (straight through), as in check_layernorm"""
+    D = I["x"].shape[-1]
+    xs = I["x"].double().requires_grad_(True)
+    rs = I["r"].double().requires_grad_(True) if res else None
+    gs, bs = I["g"].double().requires_grad_(True), I["b"].double().requires_grad_(True)
+    s = xs
+    if res:
+        s = xs + (rs * m_in if m_in is not None else rs)
+        if dtype == torch.bfloat16:
+            s = s + (s.detach().to(dtype).double() - s.detach())
+    z = TF.layer_norm(s, (D,), gs, bs, eps)
+    y = TF.gelu(z) if act else z
+    if m_out is not None:
+        y = y * m_out
+    grads = torch.autograd.grad(y, [xs, gs, bs] + ([rs] if res else []), I["dy"].double())
+    return dict(y=y.detach(), s=s.detach(), gx=grads[0], dgamma=grads[1], dbeta=grads[2], gr=grads[3] if res else None)
+
+
+def ln_rows_case(out, name, rows, D, dtype, pdtype, res, act, saves=(True, False), drop=None, masks=(None, None)):
+    """one forward per `save`, and after the saving one a backward (dr and its column sum where there is a residual), against
+    ln_ref; mean / rstd against the fp64 statistics of the stored s"""
+    I = ln_inputs(rows, D, dtype, pdtype)
+    ref = ln_ref(I, dtype, act, res, *masks)
+    tol, tols = tol_for(dtype), (TOL32_SUM if dtype == torch.float32 else TOLBF)
+    xd, rd, dyd = [I[k].to(dtype) for k in ("x", "r", "dy")]
+    gd, bd = I["g"].to(pdtype), I["b"].to(pdtype)
+    drop = drop or {}
+    tag0 = f"{name}[{dtype},{pdtype}] rows={rows} D={D} res={int(res)} act={act}" + (f" p=({drop['p_in']},{drop['p_out']})" if drop else "")
+    for save in saves:
+        tag = tag0 + ("" if save else " no-save")
+        y, s, mean, rstd = ops.layernorm_fwd(xd, rd if res else None, gd, bd, 1e-5, act=act, save=save, **drop)
+        out.append((tag + " y", errd(y, ref["y"]), tol))
+        if not save:
+            continue
+        sd = s.double()
+        out.append((tag + " s", errd(s, ref["s"]), tol))
+        out.append((tag + " mean of the stored s", errd(mean, sd.mean(1)), TOL32))
+        out.append((tag + " rstd of the stored s", errd(rstd, (sd.var(1, unbiased=False) + 1e-5).rsqrt()), TOL32))
+        dx, dr, dg, db, cs = ops.layernorm_bwd(dyd, s, mean, rstd, gd, bd, act=act, need_dr=res, dr_colsum=True if res else None, **drop)
+        out.append((tag + " dx", errd(dx, ref["gx"]), tol))
+        out.append((tag + " dgamma", errd(dg, ref["dgamma"]), tols))
+        out.append((tag + " dbeta", errd(db, ref["dbeta"]), tols))
+        if res:
+            out.append((tag + " dr", errd(dr, ref["gr"]), tol))
+            out.append((tag + " dr colsum", errd(cs, ref["gr"].sum(0)), tols))
+        if ln_full_enabled() and act == 1 and not res and not drop and D == 512 and dtype == pdtype == torch.bfloat16:
+            # these launches took the GELU-table instances (chord table of the normal CDF in LDS): gelu' is within 5.7e-4
+            # absolute of the erf form the reference differentiates, a seventh of bf16's half ulp at 1, so TOLBF holds
+            out.append((tag + " dgamma, table gelu' against the erf reference", errd(dg, ref["dgamma"]), TOLBF))
+            out.append((tag + " dbeta, table gelu' against the erf reference", errd(db, ref["dbeta"]), TOLBF))
+
+
+def ln_bwd_forms(out, rows, D, dtype, act=1, grad_scale=0.37):
+    """every combination of dx_add x need_dr x dr_colsum x dr_incl_add with grad_scale != 1 on one saved forward (the template
+    instances CS x HA x HD of the full-width backward), then the three parameter sums accumulated into pre-filled sinks"""
+    I = ln_inputs(rows, D, dtype, dtype)
+    ref = ln_ref(I, dtype, act, True)
+    tol, tols = tol_for(dtype), (TOL32_SUM if dtype == torch.float32 else TOLBF)
+    xd, rd, dyd, ed, gd, bd = [I[k].to(dtype) for k in ("x", "r", "dy", "extra", "g", "b")]
+    _y, s, mean, rstd = ops.layernorm_fwd(xd, rd, gd, bd, 1e-5, act=act, save=True)
+    gx = grad_scale * ref["gx"]
+    for add in (False, True):
+        for need_dr in (False, True):
+            for cs_on in (False, True):
+                for incl in (False, True):
+                    tag = (f"layernorm_rows[{dtype}] rows={rows} D={D} bwd dx_add={int(add)} dr={int(need_dr)} colsum={int(cs_on)} "
+                           f"incl_add={int(incl)} grad_scale={grad_scale}")
+                    dx, dr, dg, db, cs = ops.layernorm_bwd(dyd, s, mean, rstd, gd, bd, act=act, grad_scale=grad_scale, need_dr=need_dr,
+                                                           dr_colsum=True if cs_on else None, dx_add=ed if add else None, dr_incl_add=incl)
+                    rdx = gx + I["extra"].double() if add else gx
+                    rdr = rdx if (add and incl) else gx
+                    out.append((tag + " dx", errd(dx, rdx), tol))
+                    out.append((tag + " dgamma", errd(dg, ref["dgamma"]), tols))
+                    out.append((tag + " dbeta", errd(db, ref["dbeta"]), tols))
+                    if need_dr:
+                        out.append((tag + " dr", errd(dr, rdr), tol))
+                    if cs_on:
+                        out.append((tag + " dr colsum", errd(cs, rdr.sum(0)), tols))
+    sink0 = q(30.0 * dgen(3, D, seed=21), dtype)
+    sinks = [t.to(dtype).clone() for t in sink0]
+    ops.layernorm_bwd(dyd, s, mean, rstd, gd, bd, act=act, grad_scale=grad_scale, need_dr=True, dgamma=sinks[0], dbeta=sinks[1],
+                      dr_colsum=sinks[2])
+    tag = f"layernorm_rows[{dtype}] rows={rows} D={D} bwd accumulated into pre-filled sinks"
+    for nm, got, base, add_ in zip(("dgamma", "dbeta", "dr colsum"), sinks, sink0, (ref["dgamma"], ref["dbeta"], gx.sum(0))):
+        out.append((f"{tag} {nm}", errd(got, base.double() + add_), tols))
+
+
+LN_SEG_CASES = [((5, 1639), (1, 2)), ((745, 11), (0, 1))]   # (B, T) with B * T = LN_ROWS, dx_pad: the segment is shorter / far shorter than a wave's row step (2048)
+
+
+def ln_segmented(out):
+    """wavlm_layernorm_bwd_seg's padded dx layout with the segment bookkeeping carried over four or five rows per wave, into a
+    poisoned allocation (the caller has checked _poison_reaches_empty); without the full-width kernels the call has to be refused"""
+    for dtype, D in ((torch.bfloat16, 512), (torch.float32, 768)):
+        I = ln_inputs(LN_ROWS, D, dtype, dtype)
+        ref = ln_ref(I, dtype, 1, False)
+        xd, dyd, gd, bd = [I[k].to(dtype) for k in ("x", "dy", "g", "b")]
+        _y, s, mean, rstd = ops.layernorm_fwd(xd, None, gd, bd, 1e-5, act=1, save=True)
+        plain = ops.layernorm_bwd(dyd, s, mean, rstd, gd, bd, act=1)
+        for (Bn, Tn), (fp, bp) in LN_SEG_CASES:
+            assert Bn * Tn == LN_ROWS
+            tag = f"layernorm_rows[{dtype}] D={D} segmented dx [{Bn}, {Tn}] pad=({fp},{bp})"
+            call = lambda: ops.layernorm_bwd(dyd.view(Bn, Tn, D), s.view(Bn, Tn, D), mean, rstd, gd, bd, act=1, dx_pad=(fp, bp))  # noqa: E731
+            if not ln_full_enabled():
+                out.append((tag + " refused without the full-width kernels", refused(call), 0.0))
+                continue
+            # exactly the padded allocation's size: the tensors held here leave free blocks of other sizes behind, and the
+            # caching allocator hands out the smallest block that fits
+            _poison((Bn * (fp + Tn + bp) + fp + bp) * D * dyd.element_size())
+            seg = call()
+            padded = seg[0]._padded
+            out.append((tag + " interior", errd(seg[0].reshape(LN_ROWS, D), ref["gx"]), tol_for(dtype)))
+            pads = padded.clone()
+            pads[:, fp:fp + Tn] = 0
+            out.append((tag + " pad rows exactly zero", float((pads != 0).sum().item()), 0.0))
+            out.append((tag + " dx == the unsegmented call, bit for bit", same_bits(seg[0].reshape(LN_ROWS, D), plain[0]), 0.0))
+            out.append((tag + " dgamma == the unsegmented call", same_bits(seg[2], plain[2]), 0.0))
+            out.append((tag + " dbeta == the unsegmented call", same_bits(seg[3], plain[3]), 0.0))
+
+
+def ln_refusals(out):
+    """D = 2056 (above LN_MAXC * 512) and D = 12 (no multiple of 8): check()'s error, the given sinks untouched"""
+    for D in (2056, 12):
+        x = dgen(16, D, seed=1)
+        g, b = torch.ones(D, device=DEV), torch.zeros(D, device=DEV)
+        out.append((f"layernorm_rows D={D} forward refused", refused(lambda: ops.layernorm_fwd(x, None, g, b, 1e-5)), 0.0))
+        st = torch.ones(16, device=DEV)
+        sinks = [torch.full((D,), 7.0, device=DEV) for _ in range(3)]
+        out.append((f"layernorm_rows D={D} backward refused",
+                    refused(lambda: ops.layernorm_bwd(x, x, st, st, g, b, need_dr=True, dgamma=sinks[0], dbeta=sinks[1], dr_colsum=sinks[2])), 0.0))
+        torch.cuda.synchronize()
+        out.append((f"layernorm_rows D={D} refused backward left its sinks alone", float(sum((t != 7.0).sum().item() for t in sinks)), 0.0))
+
+
+def ln_above_cap_change(out):
+    """262 149 rows x 512, bf16, LayerNorm + GELU without residual: forward grid 2048, backward grid 1024 (and the workspace of
+    1024 partial rows); inputs from a seeded device generator, reference by torch's fp64 layer_norm / gelu and autograd on the
+    device (about 1 GB per fp64 tensor), everything freed before returning"""
+    rows, D, dtype = LN_ROWS_BIG, 512, torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(77)
+    xd = torch.randn(rows, D, generator=g, device=DEV).to(dtype)
+    dyd = torch.randn(rows, D, generator=g, device=DEV).to(dtype)
+    gd = (1 + 0.1 * torch.randn(D, generator=g, device=DEV)).to(dtype)
+    bd = (0.1 * torch.randn(D, generator=g, device=DEV)).to(dtype)
+    y, s, mean, rstd = ops.layernorm_fwd(xd, None, gd, bd, 1e-5, act=1, save=True)
+    dx, _dr, dg, db, _cs = ops.layernorm_bwd(dyd, s, mean, rstd, gd, bd, act=1)
+    xs, gs, bs = [t.double().requires_grad_(True) for t in (xd, gd, bd)]
+    yr = TF.gelu(TF.layer_norm(xs, (D,), gs, bs, 1e-5))
+    gr = torch.autograd.grad(yr, [xs, gs, bs], dyd.double())
+    tag = f"layernorm_rows[{dtype}] rows={rows} D={D} LayerNorm + GELU above the cap change"
+    out.append((tag + " y", errd(y, yr), TOLBF))
+    out.append((tag + " mean", errd(mean, xs.detach().mean(1)), TOL32))
+    out.append((tag + " rstd", errd(rstd, (xs.detach().var(1, unbiased=False) + 1e-5).rsqrt()), TOL32))
+    for nm, a, r_ in zip(("dx", "dgamma", "dbeta"), (dx, dg, db), gr):
+        out.append((f"{tag} {nm}", errd(a, r_), TOLBF))
+
+
+@leaves_no_footprint
+def check_layernorm_rows():
+    """LayerNorm forward / backward with several rows per wave (LN_ROWS = 8195 and the constants beside it; the launch geometry
+    they rest on is named there): the software pipeline of the full-width kernels with its clamped last prefetch, the per-lane
+    dgamma / dbeta / colsum accumulators over four or five rows, every CS x HA x HD instance at the three widths, bf16
+    activations with fp32 parameters, the no-residual and no-save forms, the GELU-table instances, the segmented dx layout,
+    the general kernels at widths with a partly filled chunk slot, the grid caps above 131 072 rows.  Under WAVLM_LN_FULL=0
+    (tests/test_kernels_gpu.py runs the group that way in a fresh process) the same cases land in the general kernels and the
+    segmented ones must be refused.  References: fp64 torch on the device (at these sizes a CPU reference is most of the
+    run time).  Left out: the 64-bit offset regime (rows * D >= 2^31) -- it needs more than 4 GB per tensor."""
+    out = [_poison_reaches_empty(64 << 20)]   # (before this group holds any memory of its own)
+    f32, bf = torch.float32, torch.bfloat16
+    try:
+        ln_segmented(out)
+        for D in LN_WIDTHS:
+            for dtype, pdtype in ((f32, f32), (bf, bf), (bf, f32)):
+                for res in (True, False):
+                    for act in (0, 1):
+                        ln_rows_case(out, "layernorm_rows", LN_ROWS, D, dtype, pdtype, res, act)
+            for dtype in (f32, bf):
+                ln_bwd_forms(out, LN_ROWS, D, dtype)
+                # idle waves of a block (early return in the forward, zero partials in the backward); no ragged sweep
+                for rows in (1, 5, 8192):
+                    ln_rows_case(out, "layernorm_rows", rows, D, dtype, dtype, True, 0, saves=(True,))
+        for D in (8, 256, 520, 1032, 2048):   # general kernels: one chunk slot barely used, full, and partly filled at NC = 2 and 4
+            for dtype in (f32, bf):
+                ln_rows_case(out, "layernorm_rows general", LN_ROWS, D, dtype, dtype, True, int(D == 520), saves=(True,))
+        ln_rows_case(out, "layernorm_rows general", LN_ROWS_GENERAL, 256, f32, f32, True, 0)
+        ln_refusals(out)
+        _LN_RAW.clear()
+        ln_above_cap_change(out)
+    finally:
+        _LN_RAW.clear()
+        torch.cuda.empty_cache()
+    return out
+
+
+def binom_bounds(n, p_keep, tail):
+    """(lo, hi) for X ~ Binomial(n, p_keep): the largest lo with P(X < lo) <= tail and the smallest hi with P(X > hi) <= tail,
+    from the exact probabilities (log-gamma form, summed in fp64 from each end); derived here like chi2_quantile, not typed in"""
+    dev = DEV if torch.cuda.is_available() else "cpu"
+    k = torch.arange(n + 1, dtype=torch.float64, device=dev)
+    logp = (math.lgamma(n + 1) - torch.lgamma(k + 1) - torch.lgamma(n - k + 1) + k * math.log(p_keep) + (n - k) * math.log1p(-p_keep))
+    pmf = logp.exp()
+    below = pmf.cumsum(0)                     # P(X <= k)
+    above = pmf.flip(0).cumsum(0).flip(0)     # P(X >= k)
+    lo = int((below <= tail).sum().item())
+    hi = int((above > tail).sum().item()) - 1
+    return lo, hi
+
+
+def keep_fraction_lines(out, tag, counts, n, p, tail, quant):
+    """two lines: how far the largest / smallest of `counts` (kept cells out of n each) lies above / below n (1 - p), against the
+    binomial quantile at `tail` per side plus `quant`, the shift of the expectation by the quantisation of p"""
+    lo, hi = binom_bounds(n, 1.0 - p, tail)
+    exp_ = n * (1.0 - p)
+    out.append((f"{tag} keep fraction above 1 - p (n = {n}, {counts.numel()} of them)", (counts.max().item() - exp_) / n, (hi - exp_) / n + quant))
+    out.append((f"{tag} keep fraction below 1 - p (n = {n}, {counts.numel()} of them)", (exp_ - counts.min().item()) / n, (exp_ - lo) / n + quant))
+
+
+LN_DROP_PAIRS = [(0.25, 0.0), (0.0, 0.25), (0.1, 0.1)]
+
+
+def ln_probe_masks(rows, D, dtype, drop):
+    """the keep masks of a launch, read out of a probe launch with the same (p_in, seed_in, p_out, seed_out): x = 0, r = 1,
+    gamma = 0, beta = 1, no activation give s = keep_in * scale_in and y = keep_out * scale_out in every cell"""
+    z, o = torch.zeros(rows, D, dtype=dtype, device=DEV), torch.ones(rows, D, dtype=dtype, device=DEV)
+    yp, sp, _, _ = ops.layernorm_fwd(z, o, torch.zeros(D, dtype=dtype, device=DEV), torch.ones(D, dtype=dtype, device=DEV), 1e-5,
+                                     act=0, save=True, **drop)
+    return sp != 0, yp != 0, sp, yp
+
+
+@leaves_no_footprint
+def check_layernorm_dropout_ref():
+    """LayerNorm with input- and output-side dropout against the fp64 reference that applies the SAME masks (recovered in full
+    by a probe launch: the mask is a function of seeds, row and column only) with scale 1 / (1 - p): y, s, dx, dr, dgamma, dbeta
+    and the dr column sum at LN_ROWS rows, where forward (1024 blocks) and backward (512) hand rows to waves differently while
+    regenerating one mask; p = 0.1 is quantised to 6554 / 65 536, a scale 7e-6 off 1 / 0.9 and well inside TOL32.  Then the law
+    of the recovered masks at D = 1024: overall, per-row and per-column keep fractions inside the binomial quantiles at a
+    family-wise tail of 1e-6 (+ 1 / 65 536 for the quantisation of p)."""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    rows = LN_ROWS
+    cases = [(D, dtype, pp, 0) for D in LN_WIDTHS for dtype in (f32, bf) for pp in LN_DROP_PAIRS]
+    cases += [(768, dtype, (0.1, 0.1), 1) for dtype in (f32, bf)]
+    cases += [(520, dtype, (0.1, 0.1), 0) for dtype in (f32, bf)]   # general kernels: the forward with dropout is capped at 1024 blocks too
+    stat_masks = []
+    try:
+        for D, dtype, (p_in, p_out), act in cases:
+            drop = dict(p_in=p_in, seed_in=0x9E3779B97F4A7C15 ^ D, p_out=p_out, seed_out=0x5851F42D4C957F2D + 3 * D)
+            keep_in, keep_out, sp, yp = ln_probe_masks(rows, D, dtype, drop)
+            m_in, m_out = keep_in.double() / (1.0 - p_in), keep_out.double() / (1.0 - p_out)
+            tag = f"layernorm_dropout_ref[{dtype}] D={D} p=({p_in},{p_out}) probe"
+            out.append((tag + " s is 0 or 1 / (1 - p_in)", errd(sp, m_in), tol_for(dtype)))
+            out.append((tag + " y is 0 or 1 / (1 - p_out)", errd(yp, m_out), tol_for(dtype)))
+            ln_rows_case(out, "layernorm_dropout_ref", rows, D, dtype, dtype, True, act, saves=(True,), drop=drop,
+                         masks=(m_in if p_in else None, m_out if p_out else None))
+            if D == 1024 and dtype == f32:
+                stat_masks += [(f"in p={p_in} (with p_out={p_out})", keep_in, p_in)] if p_in else []
+                stat_masks += [(f"out p={p_out} (with p_in={p_in})", keep_out, p_out)] if p_out else []
+        # family: per mask one overall, `rows` per-row and D per-column fractions, two sides each
+        D = 1024
+        tail = 1e-6 / (len(stat_masks) * 2 * (1 + rows + D))
+        for nm, keep, p in stat_masks:
+            tag = f"layernorm_dropout_ref mask {nm} rows={rows} D={D}"
+            keep_fraction_lines(out, tag + " overall", keep.sum().reshape(1), rows * D, p, tail, 1.0 / 65536)
+            keep_fraction_lines(out, tag + " per row", keep.sum(1), D, p, tail, 1.0 / 65536)
+            keep_fraction_lines(out, tag + " per column", keep.sum(0), rows, p, tail, 1.0 / 65536)
+    finally:
+        _LN_RAW.clear()
+        torch.cuda.empty_cache()
+    return out
+
+
+@leaves_no_footprint
+def check_colsum_rows():
+    """ops.colsum against x.double().sum(0) where colsum_finish_kernel's four-loads-in-flight loop runs (more than 192 partial
+    rows): rows 799 / 1027 / 1795 / 2048 / 8195 give 200 / 257 / 449 / 512 / 512 partial rows, so that per 64-row slice the
+    unrolled loop runs zero times, once or twice, with and without a remainder, and colsum_partial_kernel is strided at 8195
+    (CS_BLOCKS = 512 blocks of 4 rows); N = 8, 768 and CS_MAXC * 512 = 4096; ld > N; row masks; accumulation; refusals"""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    raw = dgen(8195, 4096, seed=1)
+    for dtype in (f32, bf):
+        tols = TOL32_SUM if dtype == f32 else TOLBF
+        for N in (8, 768, 4096):
+            xq = q(raw[:, :N], dtype)
+            for rows in (799, 1027, 1795, 2048, 8195):
+                xd = xq[:rows].to(dtype).contiguous()
+                out.append((f"colsum_rows[{dtype}] rows={rows} N={N}", errd(ops.colsum(xd, f32), xq[:rows].double().sum(0)), tols))
+        rows, N = 8195, 768
+        xq = q(raw[:, :N], dtype)
+        xd = xq.to(dtype).contiguous()
+        want = xq.double().sum(0)
+        wide = torch.full((rows, N + 8), float("nan"), dtype=dtype, device=DEV)
+        wide[:, :N] = xd
+        out.append((f"colsum_rows[{dtype}] rows={rows} N={N} ld=N+8", errd(ops.colsum(wide, f32, rows=rows, N=N, ld=N + 8), want), tols))
+        # masks: rows 40..43 are one block's four rows of the first sweep; rows = 44..47 (mod 2048) are ALL rows of block 11
+        ar = torch.arange(rows, device=DEV)
+        exc = ((ar >= 40) & (ar < 44)) | ((ar % 2048 >= 44) & (ar % 2048 < 48)) | (ar % 5 == 0)
+        inc = ar % 3 != 1
+        e8, i8 = exc.to(torch.uint8), inc.to(torch.uint8)
+        out.append((f"colsum_rows[{dtype}] rows={rows} exclude mask", errd(ops.colsum(xd, f32, exclude=e8), xq.double()[~exc].sum(0)), tols))
+        out.append((f"colsum_rows[{dtype}] rows={rows} include mask", errd(ops.colsum(xd, f32, include=i8), xq.double()[inc].sum(0)), tols))
+        out.append((f"colsum_rows[{dtype}] rows={rows} include + exclude masks",
+                    errd(ops.colsum(xd, f32, include=i8, exclude=e8), xq.double()[inc & ~exc].sum(0)), tols))
+        for sdt in (bf, f32):
+            sink0 = q(100.0 * dgen(N, seed=7), sdt)
+            sink = sink0.to(sdt).clone()
+            ops.colsum(xd, sdt, out=sink, accumulate=True)
+            out.append((f"colsum_rows[{dtype}] rows={rows} accumulated into a {sdt} sink", errd(sink, sink0.double() + want),
+                        TOLBF if bf in (sdt, dtype) else TOL32_SUM))
+        for Nbad in (4104, 12):
+            xb = torch.ones(64, Nbad, dtype=dtype, device=DEV)
+            sink = torch.full((Nbad,), 7.0, device=DEV)
+            out.append((f"colsum_rows[{dtype}] N={Nbad} refused", refused(lambda: ops.colsum(xb, f32, out=sink, accumulate=True)), 0.0))
+            out.append((f"colsum_rows[{dtype}] N={Nbad} refused call left its sink alone", float((sink != 7.0).sum().item()), 0.0))
+    return out
+
+
+ADAM_HP = dict(lr=5e-4, beta1=0.9, beta2=0.98, eps=1e-6)
+
+
+def adam_case(out, name, n, *, grad_dtype=torch.bfloat16, lowp=True, weight_decay=0.01, max_norm=1.0, norm=True, mult=0.5,
+              mult_dev=None, steps=(1, 2, 3)):
+    """`steps` of ops.adam_step on n elements against oracle.adam_reference_step in fp64 on the device (check_adam's tolerances)"""
+    from oracle import wavlm_oracle as O
+    p = dgen(n, seed=1)
+    gq = q(dgen(n, seed=2, scale=0.1), grad_dtype)
+    pd, md, vd = p.clone(), torch.zeros_like(p), torch.zeros_like(p)
+    gd = gq.to(grad_dtype)
+    plow = torch.empty(n, dtype=torch.bfloat16, device=DEV) if lowp else None
+    gn = ops.sumsq(gd) if norm else None
+    md_ = torch.tensor([mult_dev], device=DEV) if mult_dev is not None else None
+    fac = mult * (mult_dev if mult_dev is not None else 1.0)
+    clip = 1.0
+    if norm and max_norm > 0:
+        clip = min(1.0, max_norm / (gq.double().norm().item() * abs(fac) + 1e-6))
+    pr, mr, vr = p.double(), torch.zeros(n, dtype=torch.float64, device=DEV), torch.zeros(n, dtype=torch.float64, device=DEV)
+    for step in steps:
+        ops.adam_step(pd, md, vd, gd, plow, weight_decay=weight_decay, step=step, grad_mult=mult, grad_mult_dev=md_, gnorm_sq=gn,
+                      max_norm=max_norm, **ADAM_HP)
+        pr, mr, vr = O.adam_reference_step(pr, gq.double() * fac * clip, mr, vr, step, ADAM_HP["lr"], ADAM_HP["beta1"], ADAM_HP["beta2"],
+                                           ADAM_HP["eps"], weight_decay)
+    tag = f"flat_strided adam {name} n={n} (clip {clip:.3g})"
+    out.append((tag + " p", errd(pd, pr), 1e-5))
+    out.append((tag + " m", errd(md, mr), 1e-5))
+    out.append((tag + " v", errd(vd, vr), 1e-5))
+    if lowp:
+        out.append((tag + " low-precision copy", errd(plow, pr), 1e-2))
+
+
+@leaves_no_footprint
+def check_flat_strided():
+    """the flat grid-stride kernels past their grid caps, at the smallest n beyond the cap plus a ragged tail, against fp64
+    torch on the device: adam_step (cap 16384 blocks x 256), axpby / scale_dev (8192 x 256 elements), dropout / dropout_add
+    (8192 x 256 vectors of 8), sumsq (1024 blocks x 4096 elements), select_rows / gather_rows (4096 x 256 vectors of 8); and
+    adam_step's argument combinations at check_adam's n"""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    adam_case(out, "past the cap", 16384 * 256 + 777, steps=(1,))
+    n = 10007
+    adam_case(out, "fp32 gradient", n, grad_dtype=f32)
+    adam_case(out, "p_lowp=None", n, lowp=False)
+    adam_case(out, "weight_decay=0", n, weight_decay=0.0)
+    adam_case(out, "max_norm=0 with a norm given", n, max_norm=0.0)
+    adam_case(out, "gnorm_sq=None", n, norm=False)
+    adam_case(out, "grad_mult_dev given", n, mult_dev=0.75)
+    adam_case(out, "clip that does not bind", n, max_norm=1e4)
+    for dtype in (f32, bf):
+        tol = tol_for(dtype)
+        n = 8192 * 256 + 8
+        x, y = q(dgen(n, seed=3), dtype), q(dgen(n, seed=4), dtype)
+        yd = y.to(dtype).clone()
+        ops.axpby_(yd, x.to(dtype), 0.5, 2.0)
+        out.append((f"flat_strided axpby[{dtype}] n={n}", errd(yd, 0.5 * x.double() + 2.0 * y.double()), tol))
+        yd = torch.full((n,), float("nan"), dtype=dtype, device=DEV)
+        ops.axpby_(yd, x.to(dtype), 0.5, 0.0)
+        out.append((f"flat_strided axpby[{dtype}] n={n} b=0 (y not read)", errd(yd, 0.5 * x.double()), tol))
+        if dtype == f32:
+            xb = q(x, bf)
+            yd = y.clone()
+            ops.axpby_(yd, xb.to(bf), 0.5, 2.0)
+            out.append((f"flat_strided axpby bf16 -> fp32 n={n}", errd(yd, 0.5 * xb.double() + 2.0 * y.double()), tol))
+        z = x.to(dtype).clone()
+        ops.scale_dev_(z, torch.tensor([3.0], device=DEV), 0.5)
+        out.append((f"flat_strided scale_dev[{dtype}] n={n}", errd(z, 1.5 * x.double()), tol))
+        n = 1024 * 4096 + 5
+        x = q(dgen(n, seed=5), dtype)
+        out.append((f"flat_strided sumsq[{dtype}] n={n}", errd(ops.sumsq(x.to(dtype), 0.25), 0.25 * (x.double() ** 2).sum().reshape(1)), tol))
+        rows, D = 10923, 768   # rows * D / 8 = 1 048 608 vectors, 32 above 4096 x 256
+        x = q(dgen(rows, D, seed=6), dtype)
+        xd = x.to(dtype)
+        ar = torch.arange(rows, device=DEV)
+        sel, zero = ar % 3 == 0, ar % 5 == 0
+        for edt in ((f32,) if dtype == f32 else (bf, f32)):
+            emb = q(dgen(D, seed=7), edt)
+            got = ops.select_rows(xd, sel.to(torch.uint8), emb.to(edt), zero.to(torch.uint8))
+            ref = x.clone(); ref[sel] = q(emb, dtype); ref[zero] = 0
+            out.append((f"flat_strided select_rows[{dtype}, emb {edt}] {rows}x{D}", errd(got, ref), 1e-6))
+        got = ops.select_rows(xd, sel.to(torch.uint8), None, None)
+        ref = x.clone(); ref[sel] = 0
+        out.append((f"flat_strided select_rows[{dtype}] {rows}x{D} no emb, no zero mask", errd(got, ref), 1e-6))
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(8)).to(DEV)
+        idx[ar % 7 == 0] = -1
+        got = ops.gather_rows(xd, idx.to(torch.int32), rows)
+        ref = torch.where((idx >= 0)[:, None], x[idx.clamp_min(0)], torch.zeros_like(x))
+        out.append((f"flat_strided gather_rows[{dtype}] {rows}x{D}", errd(got, ref), 1e-6))
+        # dropout / dropout_add: two keep fractions per dtype, two sides each, in one family with a tail of 1e-6
+        n = 8 * (8192 * 256 + 3)
+        x, r = q(dgen(n, seed=9), dtype), q(dgen(n, seed=10), dtype)
+        xd, rd = x.to(dtype), r.to(dtype)
+        for p, seed in ((0.1, 42), (0.25, (1 << 40) + 17)):
+            tag = f"flat_strided dropout[{dtype}] n={n} p={p}"
+            d1, d2 = ops.dropout(rd, p, seed), ops.dropout(rd, p, seed)
+            out.append((tag + " deterministic", same_bits(d1, d2), 0.0))
+            keep = d1 != 0
+            keep_fraction_lines(out, tag, keep.sum().reshape(1), n, p, 1e-6 / 8, 2.0 ** -32)
+            one = torch.tensor(1.0, dtype=f32)
+            sc = (one / (one - torch.tensor(p, dtype=f32))).item()   # the library's fp32 1 / (1 - p)
+            want = torch.where(keep, (r * sc).to(dtype), torch.zeros_like(rd))
+            out.append((tag + " exact values on kept cells", same_bits(d1, want), 0.0))
+            da = ops.dropout_add(xd, rd, p, seed)
+            out.append((tag + " dropout_add deterministic", same_bits(da, ops.dropout_add(xd, rd, p, seed)), 0.0))
+            # same mask, same values: on x = 0 the sum IS dropout(r) (0 + v is exact in both dtypes)
+            out.append((tag + " dropout_add(0, r) == dropout(r), bit for bit", same_bits(ops.dropout_add(torch.zeros_like(xd), rd, p, seed), d1), 0.0))
+            if dtype == f32:
+                out.append((tag + " dropout_add(x, r) == x + dropout(r), bit for bit", same_bits(da, xd + d1), 0.0))
+            else:
+                out.append((tag + " dropout_add(x, r) against x + keep * r / (1 - p)", errd(da, x.double() + keep * r.double() / (1.0 - p)), tol))
+        out.append((f"flat_strided dropout_add[{dtype}] n={n} p=0 is the plain sum", errd(ops.dropout_add(xd, rd, 0.0, 5), x.double() + r.double()), tol))
+    return out
+
+
 GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
     "conv_ln_block_wide": check_conv_ln_block_wide, "convstack": check_convstack, "convstack_wide": check_convstack_wide, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
     "linear_ffn": check_linear_ffn, "activations": check_activations, "loss": check_loss, "adam": check_adam, "dropout_exact": check_dropout_exact,
     "gumbel_vq": check_gumbel_vq, "sampled_negatives": check_sampled_negatives,
+    "layernorm_rows": check_layernorm_rows, "layernorm_dropout_ref": check_layernorm_dropout_ref, "colsum_rows": check_colsum_rows,
+    "flat_strided": check_flat_strided,
 }
 
 if __name__ == "__main__":
     import json
-    name = sys.argv[1]
-    res = GROUPS[name]()
-    bad = 0
-    for (nm, e, t) in res:
-        ok = e <= t
-        bad += (not ok)
-        print(("ok   " if ok else "FAIL ") + f"{nm}: err={e:.3e} tol={t:.1e}")
-    print(json.dumps({"group": name, "n": len(res), "failed": bad}))
-    sys.exit(1 if bad else 0)
+    import time
+    total = 0
+    for name in sys.argv[1:]:   # one group, or several in one process
+        t0 = time.time()
+        res = GROUPS[name]()
+        torch.cuda.synchronize()
+        bad = 0
+        for (nm, e, t) in res:
+            ok = e <= t
+            bad += (not ok)
+            print(("ok   " if ok else "FAIL ") + f"{nm}: err={e:.3e} tol={t:.1e}")
+        print(json.dumps({"group": name, "n": len(res), "failed": bad, "seconds": round(time.time() - t0, 1)}))
+        total += bad
+    sys.exit(1 if total else 0)

@@ -25,3 +25,18 @@ def test_conv0_layer_norm_block_valu_forms():
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_checks.py"), "conv0_ln"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_layernorm_general_at_model_widths():
+    """WAVLM_LN_FULL=0 hands D = 512 / 768 / 1024 to layernorm_fwd_kernel / layernorm_bwd_kernel (the switch is read once per
+    process): the several-rows-per-wave and the dropout-reference groups in a fresh process.  There the segmented dx cases
+    assert that wavlm_layernorm_bwd_seg refuses them.  The process takes 3.4 s on an MI355X (two thirds of it start-up); the timeout is some thirty times that."""
+    import os
+    import subprocess
+    import sys
+    env = dict(os.environ, WAVLM_LN_FULL="0")
+    out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpu_checks.py"), "layernorm_rows",
+                          "layernorm_dropout_ref"], env=env, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "refused without the full-width kernels" in out.stdout
