@@ -651,8 +651,9 @@ int wavlm_diar_estimate(const void* z, int32_t z_dtype, int64_t z_stride_b, int6
  * lengths[b] clamped to [0, L] (int32 on the device), or L when lengths is NULL.
  *   table  fp32 [n][2 width + 1] on the device: per phase, the taps of the dense 2 width + o filter that lie inside the window
  *          (|t| < lowpass_filter_width), zero-filled; first int32 [n]: the dense index of table[i][0], at most o - 1.
- *   x      [B, L] WL_F32, or 2 = int16 PCM (scaled by 1 / 32768 in the kernel); y [B, L_out] WL_F32 or WL_BF16; x_stride /
- *          y_stride: row strides in elements (>= L / >= L_out).  Bytes of y outside the B x L_out view are not touched.
+ *   x      [B, L] WL_F32, or WL_I16 = 2: int16 PCM, input only (scaled by 1 / 32768 in the kernel); y [B, L_out] WL_F32 or
+ *          WL_BF16; x_stride / y_stride: row strides in elements (>= L / >= L_out).  Bytes of y outside the B x L_out view are
+ *          not touched.
  * fp32 fmaf in tap order, one thread per output and no reduction across threads: bitwise reproducible, and a row's result does
  * not depend on B or on its position in the batch.  wavlm_resample_supported: 1 if the table (n * (2 width + 2) * 4 bytes <= 48
  * KiB) and a tile of at least four frames (4 o + 2 width <= 8192 samples) fit the kernel's LDS budget; wavlm_resample_rows
@@ -667,7 +668,7 @@ int wavlm_resample_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_
  * Kaldi MFCC + deltas (ABI 28, csrc/mfcc.hip): the 39-wide features of HuBERT's first k-means iteration
  * (src/examples/hubert/simple_kmeans/dump_mfcc_feature.py:46-55: torchaudio.compliance.kaldi.mfcc(use_energy=False) at its
  * defaults, compute_deltas twice, [c | d | dd]).  W = int(0.025 sr), S = int(0.010 sr), P = the next power of two >= W.
- *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype 0 / 2; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
+ *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype WL_F32 / WL_I16; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
  *   lengths  NULL or B sample counts (clamped to [0, L]): a row ends there
  *   window [W], twiddle [P][2] = (cos, -sin)(2 pi t / P), mel_idx [23][3] = (first bin, count, offset into mel_w), mel_w
  *   [n_mel_w <= P]: filter b = sum_i mel_w[offset + i] * power[first + i] over bins < P / 2; dct [13][23] with the lifter folded
@@ -693,7 +694,7 @@ int wavlm_mfcc_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B,
  * torchaudio.transforms.MelSpectrogram(sample_rate=sr, n_fft=P, win_length=W, hop_length=S, f_min=0, f_max=sr // 2, pad=0,
  * n_mels=M) at its defaults otherwise (periodic Hann, power 2, centre, reflect, one-sided, HTK scale, no norm), + 1e-6, log.
  * The speaker model's geometry is W = 400, S = 160, P = 512, M = 40 at 16 kHz.
- *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype 0 / 2; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
+ *   x        [B, L] fp32 in [-1, 1] or int16 PCM (x_dtype WL_F32 / WL_I16; int16 is scaled by 1 / 32768 on load), row stride x_stride >= L
  *   lengths  NULL or B sample counts (clamped to [0, L]): a row ends there and is reflected at its own end
  *   window [W], twiddle [P][2] = (cos, -sin)(2 pi t / P), mel_idx [M][3] = (first bin, count, offset into mel_w), mel_w
  *   [n_mel_w <= P]: filter m = sum_i mel_w[offset + i] * power[first + i] over bins < P / 2 -- computed by the host in float64

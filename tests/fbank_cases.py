@@ -3,11 +3,13 @@ tools/gen_speaker_fbank_golden.py: computed once, never modified.  Parity signal
 quantised to int16 steps, so no mel column sits on the 1e-6 term; a case is several rows of one length.  `speaker_wave` refills the golden's waveforms from a seed."""
 import numpy as np
 
+from oracle_cache import OracleCache
+
 TILE = 56   # csrc/fbank.hip FB_NF: frames per workgroup
 LENGTHS = (257, 1600, 16037)   # 2 frames, both under both reflections; last frame centred on the end; one tile + 45 frames
 GOLDEN_LENGTHS = (24000, 16037, 24000, 11000)
 
-_SIGNALS, _REFS = {}, {}
+_SIGNALS = {}
 
 
 def signal(L, seed):
@@ -31,26 +33,14 @@ def case_rows(L):
     return [signal(L, 31 + 7 * LENGTHS.index(L) + i) for i in range({257: 8, 1600: 4, 16037: 2}[L])]
 
 
-def refs(pcm):
-    """(float64 oracle, float32 oracle) [T, 40] of pcm / 32768"""
+def _reference(x, dtype):
     from unispeech_amd.fbank import fbank_reference
-    key = pcm.tobytes()
-    if key not in _REFS:
-        x = pcm.astype(np.float64) / 32768.0
-        r64, r32 = fbank_reference(x, dtype=np.float64), fbank_reference(x, dtype=np.float32)
-        r64.setflags(write=False)
-        r32.setflags(write=False)
-        _REFS[key] = (r64, r32)
-    return _REFS[key]
+    return fbank_reference(x, dtype=dtype)
 
 
-def e32(rows):
-    """E32[m]: per mel column the largest |float32 oracle - float64 oracle| over every frame of the case's rows"""
-    e = np.zeros(40)
-    for pcm in rows:
-        r64, r32 = refs(pcm)
-        e = np.maximum(e, np.abs(r32.astype(np.float64) - r64).max(0))
-    return e
+_ORACLE = OracleCache(_reference, 40)
+refs = _ORACLE.refs   # refs(pcm) -> (float64 oracle, float32 oracle) [T, 40] of pcm / 32768
+e32 = _ORACLE.e32     # e32(rows) -> E32[m]: per mel column the largest |float32 oracle - float64 oracle| over the rows' frames
 
 
 def speaker_wave(seed, L, speaker):

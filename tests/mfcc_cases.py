@@ -3,9 +3,11 @@ modified.  Signals are broadband -- white noise plus a tone that sweeps from 300
 amplitude envelope -- and quantised to int16 steps, so low-energy mel bands are not pure rounding noise."""
 import numpy as np
 
+from oracle_cache import OracleCache
+
 TILE = 56   # csrc/mfcc.hip MF_FT: output frames per workgroup
 
-_SIGNALS, _REFS, _LABEL = {}, {}, {}
+_SIGNALS, _LABEL = {}, {}
 
 
 def signal(L, sr, seed, zero=None):
@@ -26,27 +28,14 @@ def signal(L, sr, seed, zero=None):
     return _SIGNALS[key]
 
 
-def refs(pcm, sr):
-    """(float64 oracle, float32 oracle) [frames, 39] of pcm / 32768"""
+def _reference(x, dtype, sr):
     from unispeech_amd.mfcc import mfcc_reference
-    key = (pcm.tobytes(), sr)
-    if key not in _REFS:
-        x = pcm.astype(np.float64) / 32768.0
-        r64, r32 = mfcc_reference(x, sr, np.float64), mfcc_reference(x, sr, np.float32)
-        r64.setflags(write=False)
-        r32.setflags(write=False)
-        _REFS[key] = (r64, r32)
-    return _REFS[key]
+    return mfcc_reference(x, sr, dtype)
 
 
-def e32(rows, sr):
-    """E32[j]: per output column the largest |float32 oracle - float64 oracle| over every frame of the case's rows"""
-    e = np.zeros(39)
-    for pcm in rows:
-        r64, r32 = refs(pcm, sr)
-        if len(r64):
-            e = np.maximum(e, np.abs(r32.astype(np.float64) - r64).max(0))
-    return e
+_ORACLE = OracleCache(_reference, 39)
+refs = _ORACLE.refs   # refs(pcm, sr) -> (float64 oracle, float32 oracle) [frames, 39] of pcm / 32768
+e32 = _ORACLE.e32     # e32(rows, sr) -> E32[j]: per column the largest |float32 oracle - float64 oracle| over the rows' frames
 
 
 def lengths(sr):

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("WAVLM_HIP_LIB") or os.path.join(_HERE, "lib", "libwav
 _lib = None
 ABI_VERSION = 29  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
 
-F32, BF16 = 0, 1
+F32, BF16, I16 = 0, 1, 2   # csrc/common.hpp WL_F32, WL_BF16, WL_I16 (16-bit PCM: input only)
 
 c_i32, c_i64, c_u64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 

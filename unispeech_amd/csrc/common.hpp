@@ -13,7 +13,7 @@
 #define WL_ELAUNCH (-2)
 #define WL_ENOMEM (-3)
 
-enum { WL_F32 = 0, WL_BF16 = 1 };
+enum { WL_F32 = 0, WL_BF16 = 1, WL_I16 = 2 };  // WL_I16 (16-bit PCM): input only, csrc/wave_input.hpp
 
 typedef unsigned short bf16_t;  // raw bf16 bits
 

@@ -9,8 +9,9 @@
 // (unispeech_amd/fbank.py); no sine or cosine is evaluated here.
 //
 // One launch.  A workgroup of 4 waves owns FB_NF = 56 frames of one row.  The (FB_NF - 1) S + W samples under the tile's windows
-// go to LDS once, int16 scaled by 1 / 32768 and the reflection resolved while staging (the P - W samples of a frame the window
-// zeroes are never read).  A wave takes one frame at a time through fft_wave.hpp's transform -- the real P-point transform as
+// go to LDS once, the reflection resolved while staging (wave_input.hpp: the input layer shared with resample.hip and mfcc.hip;
+// the P - W samples of a frame the window zeroes are never read).  The tables are staged and a wave takes one frame at a time
+// through fft_wave.hpp -- the real P-point transform as
 // the complex P / 2-point one and the split, shared with mfcc.hip; here the values stay fp64 in LDS between the passes (the
 // products sample x window and the twiddles are fp32, the power spectrum is rounded to fp32 once) -- so an all-zero frame has
 // an all-zero spectrum and gives log(1e-6f) rounded to fp32.  Mel: lane m, m + 64 runs over its filter's own bins in order, the
@@ -20,6 +21,7 @@
 // start at frame 0 of every row): a row's features are bit-identical wherever the row sits in the batch.
 #include "common.hpp"
 #include "fft_wave.hpp"
+#include "wave_input.hpp"
 #include "../../include/wavlm_hip.h"
 
 #define FB_NT 256
@@ -27,8 +29,6 @@
 #define FB_NF 56                       // frames per workgroup (a multiple of FB_WAVES)
 #define FB_MAX_MEL 128
 #define FB_LDS_BYTES (80 * 1024)       // two workgroups per CU
-
-enum { FB_I16 = 2 };  // input only: 16-bit PCM
 
 // LDS carve-up in floats; the float2 and double2 regions come first (16-byte alignment)
 struct fb_layout { int tw, fft, win, melw, meli, x, total; };
@@ -52,10 +52,6 @@ static inline int fb_supported(int64_t W, int64_t S, int64_t P, int64_t M) {
 
 static inline __host__ __device__ int64_t fb_frames(int64_t len, int64_t S, int64_t P) { return len <= P / 2 ? 0 : 1 + len / S; }
 
-__device__ __forceinline__ float fb_load(const void* x, long i, int dt) {
-  return dt == FB_I16 ? (float)((const short*)x)[i] * (1.0f / 32768.0f) : ((const float*)x)[i];
-}
-
 __global__ __launch_bounds__(FB_NT) void fbank_kernel(const void* __restrict__ x, int x_dt, long x_stride, long L,
     const int* __restrict__ lengths, int W, int S, int P, int M, const float* __restrict__ window,
     const float* __restrict__ twiddle, const int* __restrict__ mel_idx, const float* __restrict__ mel_w, int n_mel_w,
@@ -73,41 +69,19 @@ __global__ __launch_bounds__(FB_NT) void fbank_kernel(const void* __restrict__ x
   const long t0 = (long)blockIdx.x * FB_NF;                 // first frame of the tile
   long t1 = t0 + FB_NF;
   if (t1 > Tmax) t1 = Tmax;
-  long len = L;
-  if (lengths) { const long l = lengths[b]; len = l < 0 ? 0 : (l < L ? l : L); }
+  const long len = wave_row_len(lengths, b, L);
   const long m = fb_frames(len, S, P);                      // this row's frames; [m, Tmax) is written as zero
   float* yrow = y + (size_t)b * y_stride;
   const long tv = m < t0 ? t0 : (m < t1 ? m : t1);          // the tile's frames [tv, t1) do not exist in this row
   for (long q = tv * M + tid; q < t1 * M; q += FB_NT) yrow[q] = 0.f;
   if (tv == t0) return;                                     // nothing of the row reaches this tile
-  // tables
-  for (int k = tid; k < P; k += FB_NT) s_tw[k] = make_float2(twiddle[2 * k], twiddle[2 * k + 1]);
-  for (int k = tid; k < W; k += FB_NT) s_win[k] = window[k];
-  const int nw = n_mel_w < P ? n_mel_w : P;
-  for (int k = tid; k < P; k += FB_NT) s_melw[k] = k < nw ? mel_w[k] : 0.f;
-  for (int f = tid; f < M; f += FB_NT) {                    // a filter stays inside the H bins and the nw weights whatever it holds
-    int first = mel_idx[3 * f], count = mel_idx[3 * f + 1], off = mel_idx[3 * f + 2];
-    first = first < 0 ? 0 : (first > H ? H : first);
-    off = off < 0 ? 0 : (off > nw ? nw : off);
-    if (count > H - first) count = H - first;
-    if (count > nw - off) count = nw - off;
-    if (count < 0) count = 0;
-    s_meli[3 * f] = first; s_meli[3 * f + 1] = count; s_meli[3 * f + 2] = off;
-  }
+  mf_stage_tables(s_tw, s_win, s_melw, s_meli, twiddle, window, mel_idx, mel_w, n_mel_w, M, W, P, tid, FB_NT);
   // samples under the windows of the tile's frames: s_x[k] = x[reflect(t0 S - P / 2 + w0 + k)], w0 the window's offset in the
   // frame.  Every index a frame of the row reaches lands in [0, len) after one reflection (len > P / 2, t S <= len); the trips
   // that round the frame count up to the waves read past that and take zero.
   const int w0 = (P - W) / 2;
   const int nfr = (int)(((tv - t0) + FB_WAVES - 1) / FB_WAVES) * FB_WAVES;   // <= FB_NF
-  const void* xrow = (const char*)x + (size_t)b * x_stride * (x_dt == FB_I16 ? 2 : 4);
-  const int span = (nfr - 1) * S + W;
-  const long g0 = t0 * S - H + w0;
-  for (int k = tid; k < span; k += FB_NT) {
-    long g = g0 + k;
-    if (g < 0) g = -g;
-    if (g >= len) g = 2 * (len - 1) - g;
-    s_x[k] = (g >= 0 && g < len) ? fb_load(xrow, g, x_dt) : 0.f;
-  }
+  wave_stage<true>(s_x, wave_row(x, b, x_stride, x_dt), x_dt, t0 * S - H + w0, (nfr - 1) * S + W, len, tid, FB_NT);
   __syncthreads();
 
   double2* bufA = (double2*)(fb_lds + lo.fft) + (size_t)wave * 2 * H;
@@ -156,19 +130,15 @@ int64_t wavlm_fbank_frames(int64_t len, int32_t S, int32_t P) {
 int wavlm_fbank_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
                      int32_t S, int32_t P, int32_t M, const float* window, const float* twiddle, const int32_t* mel_idx,
                      const float* mel_w, int32_t n_mel_w, float* y, int64_t y_stride, int64_t Tmax, void* stream) {
-  if (!x || !y || !window || !twiddle || !mel_idx || !mel_w || B <= 0 || B > 65535 || L <= 0) return WL_EINVAL;
-  if (x_dtype != WL_F32 && x_dtype != FB_I16) return WL_EINVAL;
+  if (wave_check_input(x, x_dtype, x_stride, B, L, INT64_MAX >> 8) != WL_OK) return WL_EINVAL;
+  if (!y || !window || !twiddle || !mel_idx || !mel_w) return WL_EINVAL;
   if (!fb_supported(W, S, P, M) || n_mel_w < 0) return WL_EINVAL;
-  if (L > (INT64_MAX >> 8) || x_stride < L) return WL_EINVAL;
   if (Tmax < fb_frames(L, S, P) || Tmax > (INT64_MAX >> 8) / M || y_stride < Tmax * M) return WL_EINVAL;   // no row is cut short
   if (Tmax == 0) return WL_OK;
   const int64_t tiles = (Tmax + FB_NF - 1) / FB_NF;
   if (tiles > 0x7fffffffLL) return WL_EINVAL;
   const size_t smem = (size_t)fb_carve(W, S, P).total * sizeof(float);
-  // set on every such call: the attribute is per device, and a flag kept here would be neither per device nor thread-safe
-  if (smem > 48 * 1024 &&
-      hipFuncSetAttribute((const void*)fbank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS_BYTES) != hipSuccess)
-    return WL_ELAUNCH;
+  if (wl_dynamic_lds(fbank_kernel, smem, FB_LDS_BYTES) != WL_OK) return WL_ELAUNCH;
   WL_LAUNCH(fbank_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(FB_NT), smem, (hipStream_t)stream, x, (int)x_dtype,
             (long)x_stride, (long)L, lengths, (int)W, (int)S, (int)P, (int)M, window, twiddle, mel_idx, mel_w, (int)n_mel_w, y,
             (long)y_stride, (long)Tmax);

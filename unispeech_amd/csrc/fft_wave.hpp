@@ -1,6 +1,7 @@
-// The wave-per-frame real transform shared by csrc/mfcc.hip and csrc/fbank.hip: the real P-point transform of a frame y is the
-// complex H = P / 2-point transform of z[n] = y[2n] + i y[2n + 1] -- Stockham radix-4 passes (one radix-2 pass when log2 H is
-// odd) between two wave-private LDS buffers, one butterfly per lane and pass at P = 512 -- and the split
+// The table staging (mf_stage_tables) and the wave-per-frame real transform shared by csrc/mfcc.hip and csrc/fbank.hip: the
+// real P-point transform of a frame y is the complex H = P / 2-point transform of z[n] = y[2n] + i y[2n + 1] -- Stockham
+// radix-4 passes (one radix-2 pass when log2 H is odd) between two wave-private LDS buffers, one butterfly per lane and pass at
+// P = 512 -- and the split
 //   X[k] = (Z[k] + conj Z[H - k]) / 2 + w_P^k (Z[k] - conj Z[H - k]) / 2i,      k < H
 // so an all-zero frame has an all-zero spectrum exactly.  Twiddles tw[t] = exp(-2 pi i t / P), t < P, come from the host (float64
 // rounded to fp32 once); no sine or cosine is evaluated here.  Every wave of the workgroup must make the same number of calls:
@@ -21,6 +22,29 @@ __device__ __forceinline__ void mf_put(float2& o, double x, double y) { o = mf_n
 __device__ __forceinline__ void mf_put(double2& o, double x, double y) { o = make_double2(x, y); }
 __device__ __forceinline__ mf_c64 mf_cmul(mf_c64 a, float2 w) {
   return {a.x * (double)w.x - a.y * (double)w.y, a.x * (double)w.y + a.y * (double)w.x};
+}
+
+// the tables a workgroup of nt threads stages once: twiddles as float2 [P], the window [W], the mel weights padded with zeros to
+// [P], and per filter (first bin, count, offset into the weights) [nfilt][3], clamped so that a filter stays inside the H = P / 2
+// bins and the nw weights whatever the host's table holds
+__device__ __forceinline__ void mf_stage_tables(float2* s_tw, float* s_win, float* s_melw, int* s_meli,
+                                                const float* __restrict__ twiddle, const float* __restrict__ window,
+                                                const int* __restrict__ mel_idx, const float* __restrict__ mel_w, int n_mel_w,
+                                                int nfilt, int W, int P, int tid, int nt) {
+  const int H = P / 2;
+  for (int k = tid; k < P; k += nt) s_tw[k] = make_float2(twiddle[2 * k], twiddle[2 * k + 1]);
+  for (int k = tid; k < W; k += nt) s_win[k] = window[k];
+  const int nw = n_mel_w < P ? n_mel_w : P;
+  for (int k = tid; k < P; k += nt) s_melw[k] = k < nw ? mel_w[k] : 0.f;
+  for (int f = tid; f < nfilt; f += nt) {
+    int first = mel_idx[3 * f], count = mel_idx[3 * f + 1], off = mel_idx[3 * f + 2];
+    first = first < 0 ? 0 : (first > H ? H : first);
+    off = off < 0 ? 0 : (off > nw ? nw : off);
+    if (count > H - first) count = H - first;
+    if (count > nw - off) count = nw - off;
+    if (count < 0) count = 0;
+    s_meli[3 * f] = first; s_meli[3 * f + 1] = count; s_meli[3 * f + 2] = off;
+  }
 }
 
 // one Stockham pass of radix R over H points: Ns = product of the radices before it; twiddles w_H^t = tw[2 t]

@@ -9,9 +9,9 @@
 //
 // One launch.  A workgroup of 4 waves owns MF_FT = 56 output frames of one row and computes the cepstra of MF_NF = 64 frames:
 // its own and 4 on either side, which is what the second-order delta reaches, so no cepstrum, spectrum or log-mel value ever
-// goes to HBM and nothing is exchanged between workgroups.  The (MF_NF - 1) S + W samples of the tile go to LDS once (int16
-// scaled by 1 / 32768, samples outside [0, len) as zero).  A wave takes one frame at a time (fft_wave.hpp, shared with
-// fbank.hip, holds the transform): the real P-point transform is the
+// goes to HBM and nothing is exchanged between workgroups.  The (MF_NF - 1) S + W samples of the tile go to LDS once (wave_input.hpp:
+// the input layer shared with resample.hip and fbank.hip).  A wave takes one frame at a time (fft_wave.hpp, shared with
+// fbank.hip, holds the table staging and the transform): the real P-point transform is the
 // complex P / 2-point transform of z[n] = y[2n] + i y[2n + 1] -- Stockham radix-4 passes (one radix-2 pass when log2(P / 2) is
 // odd) between two wave-private LDS buffers, one butterfly per lane and pass at P = 512 -- and the split
 //   X[k] = (Z[k] + conj Z[H - k]) / 2 + w_P^k (Z[k] - conj Z[H - k]) / 2i,      H = P / 2, k < H
@@ -21,6 +21,7 @@
 // 0 of every row): a row's features are bit-identical wherever the row sits in the batch and whatever the other rows hold.
 #include "common.hpp"
 #include "fft_wave.hpp"
+#include "wave_input.hpp"
 #include "../../include/wavlm_hip.h"
 
 #define MF_NT 256
@@ -32,8 +33,6 @@
 #define MF_NMEL 23
 #define MF_NCEP 13
 #define MF_LDS_BYTES (80 * 1024)
-
-enum { MF_I16 = 2 };  // input only: 16-bit PCM
 
 // LDS carve-up in floats; the two float2 regions come first (8-byte alignment)
 struct mf_layout { int tw, fft, win, melw, meli, dct, x, c, d, total; };
@@ -60,10 +59,6 @@ static inline int mf_supported(int64_t W, int64_t S, int64_t P) {
 
 static inline int64_t mf_frames(int64_t len, int64_t W, int64_t S) { return len < W ? 0 : 1 + (len - W) / S; }
 
-__device__ __forceinline__ float mf_load(const void* x, long i, int dt) {
-  return dt == MF_I16 ? (float)((const short*)x)[i] * (1.0f / 32768.0f) : ((const float*)x)[i];
-}
-
 // sum_k k v[k + 2] / 10 as differences of the mirrored pairs: a constant stretch (digital silence at the floor) gives exactly 0
 __device__ __forceinline__ float mf_delta(const float* v) { return ((v[3] - v[1]) + 2.0f * (v[4] - v[0])) / 10.0f; }
 
@@ -87,37 +82,17 @@ __global__ __launch_bounds__(MF_NT) void mfcc_kernel(const void* __restrict__ x,
   const long t0 = (long)blockIdx.x * MF_FT;                 // first output frame of the tile
   long t1 = t0 + MF_FT;
   if (t1 > Mmax) t1 = Mmax;
-  long len = L;
-  if (lengths) { const long l = lengths[b]; len = l < 0 ? 0 : (l < L ? l : L); }
+  const long len = wave_row_len(lengths, b, L);
   const long m = len < W ? 0 : 1 + (len - W) / S;           // this row's frames; [m, Mmax) is written as zero
   float* yrow = y + (size_t)b * y_stride;
   if (t0 >= m) {                                            // nothing of the row reaches this tile
     for (long q = t0 * ncol + tid; q < t1 * ncol; q += MF_NT) yrow[q] = 0.f;
     return;
   }
-  // tables
-  for (int k = tid; k < P; k += MF_NT) s_tw[k] = make_float2(twiddle[2 * k], twiddle[2 * k + 1]);
-  for (int k = tid; k < W; k += MF_NT) s_win[k] = window[k];
-  const int nw = n_mel_w < P ? n_mel_w : P;
-  for (int k = tid; k < P; k += MF_NT) s_melw[k] = k < nw ? mel_w[k] : 0.f;
-  if (tid < MF_NMEL) {                                      // a filter stays inside the H bins and the nw weights whatever it holds
-    int first = mel_idx[3 * tid], count = mel_idx[3 * tid + 1], off = mel_idx[3 * tid + 2];
-    first = first < 0 ? 0 : (first > H ? H : first);
-    off = off < 0 ? 0 : (off > nw ? nw : off);
-    if (count > H - first) count = H - first;
-    if (count > nw - off) count = nw - off;
-    if (count < 0) count = 0;
-    s_meli[3 * tid] = first; s_meli[3 * tid + 1] = count; s_meli[3 * tid + 2] = off;
-  }
+  mf_stage_tables(s_tw, s_win, s_melw, s_meli, twiddle, window, mel_idx, mel_w, n_mel_w, MF_NMEL, W, P, tid, MF_NT);
   for (int k = tid; k < MF_NCEP * MF_NMEL; k += MF_NT) s_dct[k] = dct[k];
   // samples: s_x[k] = x[(t0 - MF_HALO) S + k]
-  const void* xrow = (const char*)x + (size_t)b * x_stride * (x_dt == MF_I16 ? 2 : 4);
-  const int span = (MF_NF - 1) * S + W;
-  const long g0 = (t0 - MF_HALO) * S;
-  for (int k = tid; k < span; k += MF_NT) {
-    const long g = g0 + k;
-    s_x[k] = (g >= 0 && g < len) ? mf_load(xrow, g, x_dt) : 0.f;
-  }
+  wave_stage(s_x, wave_row(x, b, x_stride, x_dt), x_dt, (t0 - MF_HALO) * S, (MF_NF - 1) * S + W, len, tid, MF_NT);
   __syncthreads();
 
   float2* bufA = (float2*)(mf_lds + lo.fft) + (size_t)wave * 2 * H;
@@ -226,20 +201,16 @@ int64_t wavlm_mfcc_frames(int64_t len, int32_t W, int32_t S) {
 int wavlm_mfcc_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
                     int32_t S, int32_t P, const float* window, const float* twiddle, const int32_t* mel_idx, const float* mel_w,
                     int32_t n_mel_w, const float* dct, float* y, int64_t y_stride, int64_t Mmax, int32_t ncol, void* stream) {
-  if (!x || !y || !window || !twiddle || !mel_idx || !mel_w || !dct || B <= 0 || B > 65535 || L <= 0) return WL_EINVAL;
-  if (x_dtype != WL_F32 && x_dtype != MF_I16) return WL_EINVAL;
+  if (wave_check_input(x, x_dtype, x_stride, B, L, INT64_MAX >> 8) != WL_OK) return WL_EINVAL;
+  if (!y || !window || !twiddle || !mel_idx || !mel_w || !dct) return WL_EINVAL;
   if (ncol != MF_NCEP && ncol != 3 * MF_NCEP) return WL_EINVAL;
   if (!mf_supported(W, S, P) || n_mel_w < 0) return WL_EINVAL;
-  if (L > (INT64_MAX >> 8) || x_stride < L) return WL_EINVAL;
   if (Mmax < mf_frames(L, W, S) || Mmax > (INT64_MAX >> 8) || y_stride < Mmax * ncol) return WL_EINVAL;   // no row is cut short
   if (Mmax == 0) return WL_OK;
   const int64_t tiles = (Mmax + MF_FT - 1) / MF_FT;
   if (tiles > 0x7fffffffLL) return WL_EINVAL;
   const size_t smem = (size_t)mf_carve(W, S, P).total * sizeof(float);
-  // set on every such call: the attribute is per device, and a flag kept here would be neither per device nor thread-safe
-  if (smem > 48 * 1024 &&
-      hipFuncSetAttribute((const void*)mfcc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS_BYTES) != hipSuccess)
-    return WL_ELAUNCH;
+  if (wl_dynamic_lds(mfcc_kernel, smem, MF_LDS_BYTES) != WL_OK) return WL_ELAUNCH;
   WL_LAUNCH(mfcc_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(MF_NT), smem, (hipStream_t)stream, x, (int)x_dtype,
             (long)x_stride, (long)L, lengths, (int)W, (int)S, (int)P, window, twiddle, mel_idx, mel_w, (int)n_mel_w, dct, y,
             (long)y_stride, (long)Mmax, (int)ncol);

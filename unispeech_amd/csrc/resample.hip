@@ -8,13 +8,14 @@
 // zero where the window is) and the index `first[i]` of the first of them:
 //   y[f * n + i] = sum_{j < TC} tab[i][j] * x[f * o + first[i] + j - width]          (x = 0 outside [0, len))
 // One launch; a workgroup owns FT frames (FT * n consecutive outputs) of one row.  The table, `first` and the FT * o + 2 * width
-// input samples the tile touches go to LDS once (int16 PCM is scaled by 1 / 32768 on the way, samples at or beyond the row's
-// length become zero there), so HBM sees every input sample once per tile (+ 2 * width of overlap) and every output once.
+// input samples the tile touches go to LDS once (wave_input.hpp: the input layer shared with mfcc.hip and fbank.hip), so HBM
+// sees every input sample once per tile (+ 2 * width of overlap) and every output once.
 // A thread computes RS outputs of ONE phase, FT / RS frames apart: each tap is read from LDS once for RS multiply-adds, and
 // consecutive lanes hold consecutive outputs (coalesced stores; tap rows TC dwords apart with TC odd: no bank conflicts).
 // Arithmetic: fp32 fmaf over j = 0 .. TC - 1 in that order, one thread per output: a row's result depends on nothing but the
 // row -- bit-identical wherever it sits in the batch.
 #include "common.hpp"
+#include "wave_input.hpp"
 #include "../../include/wavlm_hip.h"
 
 #define RS_NT 256
@@ -22,8 +23,6 @@
 #define RS_TILE_OUT 4096            // outputs per workgroup aimed at
 #define RS_X_FLOATS 8192            // input tile budget (32 KiB)
 #define RS_TAB_BYTES (48 * 1024)    // compact table + first-index budget
-
-enum { RS_I16 = 2 };  // input only: 16-bit PCM
 
 // frames per tile, 0 if the ratio does not fit the LDS budgets
 static inline int rs_tile_frames(int64_t o, int64_t n, int64_t width) {
@@ -39,10 +38,6 @@ static inline int rs_tile_frames(int64_t o, int64_t n, int64_t width) {
   return (int)(ft < fit ? ft : fit);
 }
 
-__device__ __forceinline__ float rs_load(const void* x, long i, int dt) {
-  return dt == RS_I16 ? (float)((const short*)x)[i] * (1.0f / 32768.0f) : ((const float*)x)[i];
-}
-
 __global__ __launch_bounds__(RS_NT) void resample_kernel(const void* __restrict__ x, int x_dt, long x_stride, long L,
     const int* __restrict__ lengths, const float* __restrict__ tab, const int* __restrict__ first, int o, int n, int width,
     int FT, void* __restrict__ y, int y_dt, long y_stride, long L_out) {
@@ -53,8 +48,7 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(const void* __restrict_
   float* s_x = (float*)(s_first + n);        // [FT * o + 2 * width]: s_x[k] = x[f0 * o - width + k]
   const int b = blockIdx.y;
   const long f0 = (long)blockIdx.x * FT;
-  long len = L;
-  if (lengths) { const long l = lengths[b]; len = l < 0 ? 0 : (l < L ? l : L); }
+  const long len = wave_row_len(lengths, b, L);
   const long len_out = (len * n + o - 1) / o;              // this row's samples; [len_out, L_out) is written as zero
   const long m0 = f0 * n;
   long m1 = m0 + (long)FT * n;
@@ -64,16 +58,11 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(const void* __restrict_
     for (long m = m0 + threadIdx.x; m < m1; m += RS_NT) st_elem(yrow, m, y_dt, 0.f);
     return;
   }
-  const void* xrow = (const char*)x + (size_t)b * x_stride * (x_dt == RS_I16 ? 2 : 4);
+  const void* xrow = wave_row(x, b, x_stride, x_dt);
   for (int k = threadIdx.x; k < n * TC; k += RS_NT) s_tab[k] = tab[k];
   const int first_max = 2 * width + o - TC;                // keeps first[i] + TC - 1 inside the dense 2 * width + o taps
   for (int k = threadIdx.x; k < n; k += RS_NT) { const int s = first[k]; s_first[k] = s < 0 ? 0 : (s > first_max ? first_max : s); }
-  const int span = FT * o + 2 * width;
-  const long g0 = f0 * o - width;
-  for (int k = threadIdx.x; k < span; k += RS_NT) {
-    const long g = g0 + k;
-    s_x[k] = (g >= 0 && g < len) ? rs_load(xrow, g, x_dt) : 0.f;
-  }
+  wave_stage(s_x, xrow, x_dt, f0 * o - width, FT * o + 2 * width, len, threadIdx.x, RS_NT);
   __syncthreads();
   const int FQ = FT / RS_RS;                               // frames between a thread's outputs
   for (int q = threadIdx.x; q < FQ * n; q += RS_NT) {
@@ -104,24 +93,18 @@ int wavlm_resample_supported(int32_t o, int32_t n, int32_t width) { return rs_ti
 int wavlm_resample_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths,
                         const float* table, const int32_t* first, int32_t o, int32_t n, int32_t width, void* y,
                         int32_t y_dtype, int64_t y_stride, void* stream) {
-  if (!x || !y || !table || !first || B <= 0 || B > 65535 || L <= 0) return WL_EINVAL;
-  if (x_dtype != WL_F32 && x_dtype != RS_I16) return WL_EINVAL;
-  if (y_dtype != WL_F32 && y_dtype != WL_BF16) return WL_EINVAL;
+  if (wave_check_input(x, x_dtype, x_stride, B, L, INT64_MAX >> 22) != WL_OK) return WL_EINVAL;   // n * L stays far inside int64
+  if (!y || !table || !first || (y_dtype != WL_F32 && y_dtype != WL_BF16)) return WL_EINVAL;
   const int FT = rs_tile_frames(o, n, width);
   if (FT <= 0) return WL_EINVAL;
-  if (L > (INT64_MAX >> 22)) return WL_EINVAL;            // n * L stays far inside int64
   const int64_t L_out = (L * n + o - 1) / o;
-  if (x_stride < L || y_stride < L_out) return WL_EINVAL;
+  if (y_stride < L_out) return WL_EINVAL;
   const int64_t frames = (L_out + n - 1) / n;
   const int64_t tiles = (frames + FT - 1) / FT;
   if (tiles > 0x7fffffffLL) return WL_EINVAL;
   const int64_t tc = 2 * (int64_t)width + 1;
   const size_t smem = (size_t)((int64_t)n * (tc + 1) + (int64_t)FT * o + 2 * (int64_t)width) * sizeof(float);
-  // set on every such call: the attribute is per device, and a flag kept here would be neither per device nor thread-safe
-  if (smem > 48 * 1024 &&
-      hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(RS_TAB_BYTES + RS_X_FLOATS * sizeof(float))) != hipSuccess)
-    return WL_ELAUNCH;
+  if (wl_dynamic_lds(resample_kernel, smem, (int)(RS_TAB_BYTES + RS_X_FLOATS * sizeof(float))) != WL_OK) return WL_ELAUNCH;
   WL_LAUNCH(resample_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(RS_NT), smem, (hipStream_t)stream, x, (int)x_dtype,
             (long)x_stride, (long)L, lengths, table, first, (int)o, (int)n, (int)width, FT, y, (int)y_dtype, (long)y_stride,
             (long)L_out);

@@ -29,10 +29,10 @@ import torch
 
 from . import _lib
 from . import ops
+from . import wavein
 
 __all__ = ["geometry", "frames", "tables", "mel_bank", "fbank", "fbank_reference", "check_options", "LOG_ADD"]
 
-I16 = 2            # csrc/fbank.hip: input dtype code of 16-bit PCM
 LOG_ADD = 1e-6     # ecapa_tdnn.py:253: the constant added before the log
 MAX_MELS = 128     # csrc/fbank.hip FB_MAX_MEL
 
@@ -105,18 +105,8 @@ def tables(sr=16000, P=512, W=400, M=40):
     mel_w) and mel_w [sum of counts]: filter m is sum_i mel_w[offset + i] * power[first + i] (an empty filter: count 0)"""
     n = np.arange(W, dtype=np.float64)
     window = 0.5 - 0.5 * np.cos(2.0 * math.pi * n / W)
-    t = np.arange(P, dtype=np.float64) * (2.0 * math.pi / P)
-    twiddle = np.stack([np.cos(t), -np.sin(t)], axis=1)
-    fb = mel_bank(sr, P, M)
-    idx, ws, off = [], [np.zeros(0)], 0
-    for m in range(M):
-        nz = np.nonzero(fb[:, m])[0]
-        first, count = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if len(nz) else (0, 0)
-        idx.append((first, count, off))
-        ws.append(fb[first:first + count, m])
-        off += count
-    return dict(W=W, P=P, M=M, window=window, twiddle=twiddle, mel_idx=np.asarray(idx, dtype=np.int32).reshape(M, 3),
-                mel_w=np.concatenate(ws))
+    mel_idx, mel_w = wavein.pack_filters(mel_bank(sr, P, M).T)
+    return dict(W=W, P=P, M=M, window=window, twiddle=wavein.twiddle(P), mel_idx=mel_idx, mel_w=mel_w)
 
 
 def _check_supported(sr, W, S, P, M):
@@ -135,10 +125,9 @@ def _device_tables(sr, P, W, M, device):
     hit = _TABLES.get(key)
     if hit is None:
         t = tables(sr, P, W, M)
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-        mel_w = t["mel_w"] if len(t["mel_w"]) else np.zeros(1)
-        hit = dict(window=f32(t["window"]), twiddle=f32(t["twiddle"]), mel_w=f32(mel_w), n_mel_w=len(t["mel_w"]),
-                   mel_idx=torch.from_numpy(np.ascontiguousarray(t["mel_idx"])).to(device))
+        hit = {k: wavein.upload(t[k], device) for k in ("window", "twiddle", "mel_idx")}
+        # the kernel wants a pointer even where no filter has a weight: one placeholder element, n_mel_w = 0
+        hit.update(mel_w=wavein.upload(t["mel_w"] if len(t["mel_w"]) else np.zeros(1), device), n_mel_w=len(t["mel_w"]))
         _TABLES[key] = hit
     return hit
 
@@ -154,46 +143,15 @@ def fbank(wavs, lengths=None, sr=16000, n_mels=40, n_fft=512, win_length=None, h
     W, S, P = geometry(sr, n_fft, win_length, hop_length)
     M = int(n_mels)
     _check_supported(sr, W, S, P, M)
-    squeeze = False
-    if isinstance(wavs, (list, tuple)):
-        if lengths is not None:
-            raise ValueError("fbank: a list of waveforms carries its own lengths")
-        if not wavs:
-            raise ValueError("fbank: an empty list of waveforms")
-        dev = ops._dev(wavs[0])
-        if any(w.dim() != 1 or w.dtype != wavs[0].dtype or w.device != dev for w in wavs):
-            raise ValueError("fbank: a list takes 1-D tensors of one dtype on one device")
-        lengths = [int(w.numel()) for w in wavs]
-        wave = torch.zeros((len(wavs), max(max(lengths), 1)), dtype=wavs[0].dtype, device=dev)
-        for r, w in enumerate(wavs):
-            wave[r, :lengths[r]] = w
-    else:
-        wave = wavs
-        dev = ops._dev(wave)
-        squeeze = wave.dim() == 1
-        if squeeze:
-            wave = wave.unsqueeze(0)
-    if wave.dtype not in (torch.float32, torch.int16):
-        raise TypeError("fbank takes float32 or int16 PCM, got %s" % wave.dtype)
-    if wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1:
-        raise ValueError("fbank takes [B, L] with B, L >= 1, got %s" % (tuple(wave.shape),))
-    B, L = wave.shape
-    if wave.stride(1) != 1 or (B > 1 and wave.stride(0) < L):
-        wave = wave.contiguous()
-    len_t = None
-    if lengths is not None:
-        len_l = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-        if len(len_l) != B:
-            raise ValueError("lengths must hold %d sample counts" % B)
-        len_t = torch.tensor([min(max(v, 0), L) for v in len_l], dtype=torch.int32).to(dev)
+    wave, B, L, xs, _, len_t, squeeze, dev = wavein.as_batch(wavs, lengths, "fbank")
     T = frames(L, S, P)
     out = torch.empty((B, T, M), dtype=torch.float32, device=dev)
     if T:
         t = _device_tables(sr, P, W, M, dev)
         _lib.check(_lib.lib().wavlm_fbank_rows(
-            ops.ptr(wave), I16 if wave.dtype == torch.int16 else _lib.F32, wave.stride(0) if B > 1 else L, B, L, ops.ptr(len_t),
-            W, S, P, M, ops.ptr(t["window"]), ops.ptr(t["twiddle"]), ops.ptr(t["mel_idx"]), ops.ptr(t["mel_w"]), t["n_mel_w"],
-            ops.ptr(out), T * M, T, ops.stream()), "wavlm_fbank_rows")
+            ops.ptr(wave), wavein.dtype_code(wave), xs, B, L, ops.ptr(len_t), W, S, P, M, ops.ptr(t["window"]),
+            ops.ptr(t["twiddle"]), ops.ptr(t["mel_idx"]), ops.ptr(t["mel_w"]), t["n_mel_w"], ops.ptr(out), T * M, T,
+            ops.stream()), "wavlm_fbank_rows")
     return out[0] if squeeze else out
 
 

@@ -26,11 +26,11 @@ import torch
 
 from . import _lib
 from . import ops
+from . import wavein
 
 __all__ = ["geometry", "num_frames", "tables", "mel_filters", "dct_lifter", "mfcc", "MfccFeatureReader", "mfcc_reference",
            "compute_deltas_reference", "check_options"]
 
-I16 = 2            # csrc/mfcc.hip: input dtype code of 16-bit PCM
 NUM_MEL, NUM_CEPS, WIDTH = 23, 13, 39
 EPS32 = 1.1920928955078125e-07   # torch.finfo(torch.float32).eps: the floor of the mel energies
 
@@ -108,18 +108,8 @@ def tables(sample_rate):
     W, S, P = geometry(sample_rate)
     n = np.arange(W, dtype=np.float64)
     window = (0.5 - 0.5 * np.cos(2.0 * math.pi * n / (W - 1))) ** 0.85
-    t = np.arange(P, dtype=np.float64) * (2.0 * math.pi / P)
-    twiddle = np.stack([np.cos(t), -np.sin(t)], axis=1)
-    filt = mel_filters(sample_rate)
-    idx, ws, off = [], [], 0
-    for b in range(NUM_MEL):
-        nz = np.nonzero(filt[b])[0]
-        first, count = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if len(nz) else (0, 0)
-        idx.append((first, count, off))
-        ws.append(filt[b, first:first + count])
-        off += count
-    return dict(W=W, S=S, P=P, window=window, twiddle=twiddle, mel_idx=np.asarray(idx, dtype=np.int32),
-                mel_w=np.concatenate(ws), dct=dct_lifter())
+    mel_idx, mel_w = wavein.pack_filters(mel_filters(sample_rate))
+    return dict(W=W, S=S, P=P, window=window, twiddle=wavein.twiddle(P), mel_idx=mel_idx, mel_w=mel_w, dct=dct_lifter())
 
 
 def _check_supported(sample_rate, W, S, P):
@@ -136,9 +126,7 @@ def _device_tables(sample_rate, device):
     hit = _TABLES.get(key)
     if hit is None:
         t = tables(sample_rate)
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-        hit = dict(window=f32(t["window"]), twiddle=f32(t["twiddle"]), mel_w=f32(t["mel_w"]), dct=f32(t["dct"]),
-                   mel_idx=torch.from_numpy(np.ascontiguousarray(t["mel_idx"])).to(device))
+        hit = {k: wavein.upload(t[k], device) for k in ("window", "twiddle", "mel_idx", "mel_w", "dct")}
         _TABLES[key] = hit
     return hit
 
@@ -152,41 +140,7 @@ def mfcc(wavs, sample_rate=16000, lengths=None, deltas=True, **kaldi_options):
     check_options(**kaldi_options)
     W, S, P = geometry(sample_rate)
     _check_supported(sample_rate, W, S, P)
-    squeeze = False
-    if isinstance(wavs, (list, tuple)):
-        if lengths is not None:
-            raise ValueError("mfcc: a list of waveforms carries its own lengths")
-        if not wavs:
-            raise ValueError("mfcc: an empty list of waveforms")
-        dev = ops._dev(wavs[0])
-        if any(w.dim() != 1 or w.dtype != wavs[0].dtype or w.device != dev for w in wavs):
-            raise ValueError("mfcc: a list takes 1-D tensors of one dtype on one device")
-        lengths = [int(w.numel()) for w in wavs]
-        wave = torch.zeros((len(wavs), max(max(lengths), 1)), dtype=wavs[0].dtype, device=dev)
-        for r, w in enumerate(wavs):
-            wave[r, :lengths[r]] = w
-    else:
-        wave = wavs
-        dev = ops._dev(wave)
-        squeeze = wave.dim() == 1
-        if squeeze:
-            wave = wave.unsqueeze(0)
-    if wave.dtype not in (torch.float32, torch.int16):
-        raise TypeError("mfcc takes float32 or int16 PCM, got %s" % wave.dtype)
-    if wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1:
-        raise ValueError("mfcc takes [B, L] with B, L >= 1, got %s" % (tuple(wave.shape),))
-    B, L = wave.shape
-    if wave.stride(1) != 1 or (B > 1 and wave.stride(0) < L):
-        wave = wave.contiguous()
-    len_t = None
-    if lengths is not None:
-        len_l = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-        if len(len_l) != B:
-            raise ValueError("lengths must hold %d sample counts" % B)
-        len_l = [min(max(v, 0), L) for v in len_l]
-        len_t = torch.tensor(len_l, dtype=torch.int32).to(dev)
-    else:
-        len_l = [L] * B
+    wave, B, L, xs, len_l, len_t, squeeze, dev = wavein.as_batch(wavs, lengths, "mfcc")
     frames = [num_frames(v, sample_rate) for v in len_l]
     Mmax = num_frames(L, sample_rate)
     ncol = WIDTH if deltas else NUM_CEPS
@@ -194,9 +148,9 @@ def mfcc(wavs, sample_rate=16000, lengths=None, deltas=True, **kaldi_options):
     if Mmax:
         t = _device_tables(sample_rate, dev)
         _lib.check(_lib.lib().wavlm_mfcc_rows(
-            ops.ptr(wave), I16 if wave.dtype == torch.int16 else _lib.F32, wave.stride(0) if B > 1 else L, B, L, ops.ptr(len_t),
-            W, S, P, ops.ptr(t["window"]), ops.ptr(t["twiddle"]), ops.ptr(t["mel_idx"]), ops.ptr(t["mel_w"]),
-            t["mel_w"].numel(), ops.ptr(t["dct"]), ops.ptr(out), Mmax * ncol, Mmax, ncol, ops.stream()), "wavlm_mfcc_rows")
+            ops.ptr(wave), wavein.dtype_code(wave), xs, B, L, ops.ptr(len_t), W, S, P, ops.ptr(t["window"]),
+            ops.ptr(t["twiddle"]), ops.ptr(t["mel_idx"]), ops.ptr(t["mel_w"]), t["mel_w"].numel(), ops.ptr(t["dct"]),
+            ops.ptr(out), Mmax * ncol, Mmax, ncol, ops.stream()), "wavlm_mfcc_rows")
     return (out[0] if squeeze else out), frames
 
 

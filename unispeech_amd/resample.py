@@ -25,10 +25,9 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops
+from . import wavein
 
 __all__ = ["sinc_table", "compact_table", "resample", "Resample", "resample_reference", "output_length"]
-
-I16 = 2   # csrc/resample.hip: input dtype code of 16-bit PCM
 
 
 def _geometry(orig, new, lowpass_filter_width=6, rolloff=0.99):
@@ -99,7 +98,7 @@ def _device_table(orig, new, device):
     hit = _TABLES.get(key)
     if hit is None:
         taps, first, width, o, n = compact_table(orig, new)
-        hit = (torch.from_numpy(taps.astype(np.float32)).to(device).contiguous(), torch.from_numpy(first).to(device), o, n, width)
+        hit = (wavein.upload(taps, device), wavein.upload(first, device), o, n, width)
         _TABLES[key] = hit
     return hit
 
@@ -114,17 +113,7 @@ def resample(wave, orig, new, lengths=None, out_dtype=None, out=None):
         return wave
     o, n, width, _ = _geometry(orig, new)
     _check_supported(orig, new, o, n, width)
-    dev = ops._dev(wave)
-    if wave.dtype not in (torch.float32, torch.int16):
-        raise TypeError("resample takes float32 or int16 PCM, got %s" % wave.dtype)
-    squeeze = wave.dim() == 1
-    if squeeze:
-        wave = wave.unsqueeze(0)
-    if wave.dim() != 2 or wave.shape[1] < 1 or wave.shape[0] < 1:
-        raise ValueError("resample takes [B, L] with B, L >= 1, got %s" % (tuple(wave.shape),))
-    B, L = wave.shape
-    if wave.stride(1) != 1 or (B > 1 and wave.stride(0) < L):
-        wave = wave.contiguous()
+    wave, B, L, xs, _, _, squeeze, dev = wavein.as_batch(wave, None, "resample", allow_list=False)
     L_out = output_length(L, o, n)
     out_dtype = out_dtype or (out.dtype if out is not None else torch.float32)
     if out_dtype not in (torch.float32, torch.bfloat16):
@@ -135,15 +124,14 @@ def resample(wave, orig, new, lengths=None, out_dtype=None, out=None):
           or (B > 1 and out.stride(0) < L_out)):
         raise ValueError("out must be a [%d, %d] %s tensor on %s with unit sample stride" % (B, L_out, out_dtype, dev))
     len_t = None
-    if lengths is not None:
+    if lengths is not None:            # a tensor or a sequence, as given: the kernel clamps
         len_t = torch.as_tensor(lengths)
         if len_t.numel() != B:
             raise ValueError("lengths must hold %d sample counts" % B)
         len_t = len_t.to(device=dev, dtype=torch.int32).contiguous()
     taps, first, o, n, width = _device_table(orig, new, dev)
-    xs = wave.stride(0) if B > 1 else L
     ys = out.stride(0) if B > 1 else L_out
-    _lib.check(_lib.lib().wavlm_resample_rows(ops.ptr(wave), I16 if wave.dtype == torch.int16 else _lib.F32, xs, B, L,
+    _lib.check(_lib.lib().wavlm_resample_rows(ops.ptr(wave), wavein.dtype_code(wave), xs, B, L,
                                               ops.ptr(len_t), ops.ptr(taps), ops.ptr(first), o, n, width, ops.ptr(out),
                                               ops.dt(out), ys, ops.stream()), "wavlm_resample_rows")
     return out[0] if squeeze else out
