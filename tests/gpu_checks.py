@@ -18,6 +18,17 @@ cap moves the shape named beside it:
   flat_strided           n just past 16384 x 256 (adam_step), 8192 x 256 (axpby, scale_dev; x 8 for dropout, dropout_add),
                          1024 x 4096 (sumsq), 4096 x 256 x 8 (select_rows, gather_rows)
 tests/test_kernels_gpu.py runs the two LayerNorm groups once more in a fresh process under WAVLM_LN_FULL=0.
+
+The kernels of loss.hip loop the same way -- 8192 blocks of 4 rows (l2norm_fwd, l2norm_bwd, ce_rows, gather_dot, rows_wsum), 8192
+blocks of one row (glu_fwd, glu_bwd), 8192 x 256 elements (act_fwd, act_bwd), 1024 blocks x 2048 elements (sum_f32, bce_logits) --
+and two groups run them there, against fp64 torch on the device:
+  masked_pred_head       MaskedPredLossFn and its kernels one by one at (S, V, F) = (1029, 504, 256), (12 805, 504, 256), (32 773, 504,
+                         256) -- the label-embedding gradient's split-K (ops.pick_split on S / 64 K tiles) at 2, 25 and its cap of 64
+                         slabs; 32 773 = 4 x 8192 + 5 rows -- (2053, 504, 768), (1500, 100, 256), (1029, 500, 256), (1029, 1000, 256),
+                         (5, 2, 8); skewed, out-of-range and zero-row inputs, need_grad=False, S = 0, target_glu at (1029, 504, 256)
+  loss_rows_capped       32 773 rows (4 x 8192 + 5) for l2norm (D = 256, 100), ce_rows (V = 101, ld = 104), gather_dot (N = 3, D = 64)
+                         and rows_wsum (D = 64); 8195 rows (8192 + 3) for glu (F = 48, 300); n = 8192 x 256 + 7 for act; n = 1024 x
+                         2048 + 5 for sum_f32 and bce_logits
 """
 import math
 import sys
@@ -2451,13 +2462,399 @@ def check_flat_strided():
     return out
 
 
+# ------------------------------------------------ the masked-prediction head at training shapes; loss.hip past its grid caps
+# Launch geometry of loss.hip the shapes below rest on (the wavlm_* entry points at the end of that file):
+LOSS_ROW_BLOCKS = 8192                       # l2norm_fwd / l2norm_bwd / ce_rows / gather_dot / rows_wsum: 4 rows per block (one per wave)
+LOSS_ROWS = 4 * LOSS_ROW_BLOCKS + 5          # = 32 773: five waves take a second row, the last sweep is ragged
+GLU_BLOCKS = 8192                            # glu_fwd / glu_bwd: one row per block
+GLU_ROWS = GLU_BLOCKS + 3                    # = 8195
+ACT_BLOCKS = 8192                            # act_fwd / act_bwd: 256 elements per block
+ACT_N = ACT_BLOCKS * 256 + 7
+RED_BLOCKS, RED_PER_BLOCK = 1024, 256 * 8    # sum_f32 / bce_logits: grid = n / 2048, capped at 1024 blocks
+RED_N = RED_BLOCKS * RED_PER_BLOCK + 5
+MP_TEMP, MP_GRAD = 0.1, 1.7                  # logit_temp of the released recipes; the cotangent of the loss
+ACT_REFS = {"relu": torch.relu, "tanh": torch.tanh, "gelu": lambda x: TF.gelu(x),
+            "gelu_accurate": lambda x: 0.5 * x * (1 + torch.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3)))}
+GLU_GATE_REFS = {"sigmoid": torch.sigmoid, "swish": lambda b: b * torch.sigmoid(b), "relu": torch.relu, "gelu": lambda b: TF.gelu(b),
+                 "bilinear": lambda b: b}
+
+
+def mp_reference(p64, e64, tgt, temp, keep=None):
+    """the head in fp64 where the inputs live: cos(p, e) / temp with each norm clamped at 1e-8, sum-reduced cross entropy over
+    the rows of `keep` (all rows if None), gradients of MP_GRAD * loss.  Returns (loss, logits of every row, dproj, demb)."""
+    pr, er = p64.clone().requires_grad_(True), e64.clone().requires_grad_(True)
+    logits = TF.normalize(pr, dim=-1, eps=1e-8) @ TF.normalize(er, dim=-1, eps=1e-8).t() / temp
+    loss = TF.cross_entropy(logits if keep is None else logits[keep], tgt if keep is None else tgt[keep], reduction="sum")
+    gp, ge = torch.autograd.grad(MP_GRAD * loss, (pr, er))
+    return loss.detach(), logits.detach(), gp, ge
+
+
+def mp_gap(l64, tgt, valid):
+    """per row, the target logit minus the best other logit (>= 0: the row counts as correct); -inf where the label lies
+    outside [0, V) -- such a row is never correct"""
+    S, V = l64.shape
+    ar = torch.arange(S, device=l64.device)
+    ts = tgt.clamp(0, V - 1)
+    other = l64.clone()
+    other[ar, ts] = float("-inf")
+    return torch.where(valid, l64[ar, ts] - other.max(-1).values, torch.full_like(l64[:, 0], float("-inf")))
+
+
+def mp_inputs(S, V, Fd, dtype, sigma, labels=None, emb_of=None):
+    """CPU draws rounded through dtype: emb = gen(V, F) (or emb_of(raw table)), labels uniform unless given, proj = emb[label]
+    + sigma * gen(S, F) -- a head that has learnt something: the target cosine stands out of the V - 1 others by about as much
+    as their maximum, so that a good share of the rows, not one in V, is correct"""
+    emb_raw = gen(V, Fd, seed=1)
+    if emb_of is not None:
+        emb_raw = emb_of(emb_raw)
+    tgt = labels if labels is not None else torch.randint(0, V, (S,), generator=torch.Generator().manual_seed(3))
+    proj = q(emb_raw[tgt] + sigma * gen(S, Fd, seed=2), dtype)
+    return proj, q(emb_raw, dtype), tgt.clone()
+
+
+def mp_compare(out, name, S, V, Fd, dtype, sigma=5.0, want_split=None, labels=None, bad=None, zero_p=None, zero_e=None):
+    """one MaskedPredLossFn.apply(proj, emb, target, 0.1, True) against mp_reference, and the head's kernels one by one through
+    direct calls on the same inputs: l2norm rows and inverse norms; the logits GEMM on the device's own stored rows; ce_rows'
+    verdict per row against the fp64 verdict on those stored rows, outside the band of twice the fp32 dot-product bound
+    gamma_F |a| |b| / temp for unit rows; its gradient and the pad columns [V, roundup(V, 8)) in a NaN-filled buffer.
+    want_split: the split of the label-embedding gradient this shape is here for (asserted on the full grid of 256 blocks).
+    bad {row: label}: labels outside [0, V); zero_p / zero_e: a proj / an emb row set to zero, compared on its own (its
+    1 / eps gradient would set the scale of the whole tensor).  Returns what the follow-up lines of a case need."""
+    f32 = torch.float32
+    tol, temp = tol_for(dtype), MP_TEMP
+    proj, emb, tgt = mp_inputs(S, V, Fd, dtype, sigma, labels)
+    for r, lab in (bad or {}).items():
+        tgt[r] = lab
+    if zero_p is not None:
+        proj[zero_p] = 0.0
+    if zero_e is not None:
+        emb[zero_e] = 0.0
+    pd, ed, td = proj.to(dtype).to(DEV), emb.to(dtype).to(DEV), tgt.to(DEV)
+    t32 = td.to(torch.int32)
+    valid = (td >= 0) & (td < V)
+    kp = torch.ones(S, dtype=torch.bool, device=DEV)
+    ke = torch.ones(V, dtype=torch.bool, device=DEV)
+    if zero_p is not None:
+        kp[zero_p] = False
+    if zero_e is not None:
+        ke[zero_e] = False
+    split = ops.pick_split(V, Fd, (S + 63) // 64)
+    tag = f"masked_pred_head[{'fp32' if dtype == f32 else 'bf16'}] {name}S={S} V={V} F={Fd} split={split}"
+    if want_split is not None and ops.grid_blocks() == 256:
+        out.append((tag + f" premise: the label-embedding gradient runs with split {want_split}", 0.0 if split == want_split else 1.0, 0.0))
+    else:
+        out.append((tag + f" the label-embedding gradient ran with split {split} on a grid of {ops.grid_blocks()} blocks", 0.0, 0.0))
+    # ---- the fp64 reference from the un-normalised inputs, and the premise that the counter has something to count
+    lossr, l64, gp, ge = mp_reference(pd.double(), ed.double(), td, temp, keep=valid if bad else None)
+    gap = mp_gap(l64, td, valid)
+    nref = int((gap >= 0).sum().item())
+    frac = nref / max(int(valid.sum().item()), 1)
+    out.append((tag + f" premise: the fp64 reference counts {100 * frac:.1f} % of the rows correct, within [40, 90]", 0.0 if 0.4 <= frac <= 0.9 else 1.0, 0.0))
+    # ---- the autograd function
+    pg, eg = pd.clone().requires_grad_(True), ed.clone().requires_grad_(True)
+    loss, nc = F.MaskedPredLossFn.apply(pg, eg, t32, temp, True)
+    dproj, demb = torch.autograd.grad((loss * MP_GRAD).sum(), (pg, eg))
+    if bad:
+        out.append((tag + " loss is NaN", 0.0 if bool(torch.isnan(loss).all()) else 1.0, 0.0))
+        out.append((tag + " dproj on the rows with a label outside [0, V) (non-zero elements)", float((dproj[~valid] != 0).sum().item()), 0.0))
+    else:
+        out.append((tag + " loss", errd(loss, lossr.reshape(1)), tol))
+    out.append((tag + " dproj", errd(dproj[kp & valid], gp[kp & valid]), 3 * tol))
+    out.append((tag + " demb", errd(demb[ke], ge[ke]), 3 * tol))
+    if zero_p is not None:
+        out.append((tag + " dproj, the zero row on its own", errd(dproj[~kp], gp[~kp]), 3 * tol))
+    if zero_e is not None:
+        out.append((tag + " demb, the zero row on its own", errd(demb[~ke], ge[~ke]), 3 * tol))
+    diff = abs(int(round(nc.item())) - nref)
+    if dtype == f32:
+        k = int(((gap.abs() < 8.0 * 2.0 ** -23 * l64.abs().max(-1).values) & valid).sum().item())
+        out.append((tag + f" n_correct (beyond the {k} near-tie rows)", float(max(0, diff - k)), 0.0))
+        out.append((tag + f" near-tie rows: {k} of {S} (cap 0.1 %)", k / S, 1e-3))
+    else:
+        out.append((tag + " n_correct", float(diff), max(2.0, 0.02 * S)))
+    # ---- the kernels one by one
+    pn, inv_p = ops.l2norm_fwd(pd, dtype)
+    en, inv_e = ops.l2norm_fwd(ed, dtype)
+    for nm, y, inv, x64, kk in (("proj", pn, inv_p, pd.double(), kp), ("emb", en, inv_e, ed.double(), ke)):
+        nr = x64.norm(dim=-1).clamp_min(1e-8)
+        out.append((tag + f" l2norm {nm} rows", errd(y, x64 / nr[:, None]), tol))
+        out.append((tag + f" l2norm {nm} inv_norm", errd(inv[kk], 1.0 / nr[kk]), tol))
+        if not bool(kk.all()):
+            out.append((tag + f" l2norm {nm} inv_norm of the zero row", errd(inv[~kk], 1.0 / nr[~kk]), tol))
+    lg = torch.full((S, V), float("nan"), dtype=f32, device=DEV)
+    ops.gemm(pn, en, lg, S, V, Fd, lda=Fd, ldb=Fd, ldc=V, alpha=1.0 / temp)
+    ls64 = pn.double() @ en.double().t() / temp
+    out.append((tag + " logits from the stored rows", errd(lg, ls64), TOL32))
+    ldd = (V + 7) // 8 * 8
+    dlog = torch.full((S, ldd), float("nan"), dtype=dtype, device=DEV)
+    _, corr = ops.ce_rows(lg, t32, V, V, dlog, ldd, 1.0)
+    gs = mp_gap(ls64, td, valid)
+    band = gs.abs() < 2.0 * Fd * 2.0 ** -24 / temp * 1.01
+    nb = int(band.sum().item())
+    out.append((tag + f" correct, row by row (mismatches outside the {nb} rows within 2 F 2^-24 / temp of a tie)",
+                float(((corr.bool() != (gs >= 0)) & ~band).sum().item()), 0.0))
+    out.append((tag + f" rows within that band: {nb} of {S} (cap 0.5 %)", nb / S, 5e-3))
+    dref = torch.softmax(lg.double(), -1)
+    dref[torch.arange(S, device=DEV), td.clamp(0, V - 1)] -= 1.0
+    dref[~valid] = 0.0
+    out.append((tag + " d loss / d logit from the device logits", errd(dlog[:, :V], dref), tol))
+    out.append((tag + f" pad columns [{V}, {ldd}) of d loss / d logit (non-zero elements)", float((dlog[:, V:] != 0).sum().item()), 0.0))
+    return dict(tag=tag, pd=pd, ed=ed, t32=t32, td=td, loss=loss, nc=nc, dproj=dproj, demb=demb, gp=gp, ge=ge)
+
+
+def mp_glu_case(out, dtype, S=1029, V=504, Fd=256, sigma=2.5):
+    """target_glu as pretrain.py composes it: emb = GLUFn(LinearFn(table[V, F], W[2F, F], b)), then the loss; against the same
+    composition in fp64.  proj is drawn around the rows of the fp64 GLU output (about half the scale of the table: sigma
+    follows it)."""
+    tol = tol_for(dtype)
+    table = q(gen(V, Fd, seed=11), dtype)
+    W = q(gen(2 * Fd, Fd, seed=12, scale=1.0 / math.sqrt(Fd)), dtype)
+    b = q(0.1 * gen(2 * Fd, seed=13), dtype)
+    tgt = torch.randint(0, V, (S,), generator=torch.Generator().manual_seed(3))
+    proj = q(TF.glu(TF.linear(table.double(), W.double(), b.double()), -1).float()[tgt] + sigma * gen(S, Fd, seed=2), dtype)
+    td = tgt.to(DEV)
+    ref = [t.to(DEV).double().requires_grad_(True) for t in (proj, table, W, b)]
+    e64 = TF.glu(TF.linear(ref[1], ref[2], ref[3]), -1)
+    l64 = TF.normalize(ref[0], dim=-1, eps=1e-8) @ TF.normalize(e64, dim=-1, eps=1e-8).t() / MP_TEMP
+    lossr = TF.cross_entropy(l64, td, reduction="sum")
+    gr = torch.autograd.grad(MP_GRAD * lossr, ref)
+    frac = (mp_gap(l64.detach(), td, torch.ones_like(td, dtype=torch.bool)) >= 0).double().mean().item()
+    dev = [t.to(dtype).to(DEV).requires_grad_(True) for t in (proj, table, W, b)]
+    embd = F.GLUFn.apply(F.LinearFn.apply(dev[1].contiguous(), dev[2], dev[3]))
+    loss, _ = F.MaskedPredLossFn.apply(dev[0], embd, td.to(torch.int32), MP_TEMP, True)
+    gd = torch.autograd.grad((loss * MP_GRAD).sum(), dev)
+    tag = f"masked_pred_head[{'fp32' if dtype == torch.float32 else 'bf16'}] target_glu S={S} V={V} F={Fd}"
+    out.append((tag + f" premise: the fp64 reference counts {100 * frac:.1f} % of the rows correct, within [40, 90]", 0.0 if 0.4 <= frac <= 0.9 else 1.0, 0.0))
+    out.append((tag + " loss", errd(loss, lossr.detach().reshape(1)), tol))
+    for nm, a, r in zip(("dproj", "dtable", "dW", "db"), gd, gr):
+        out.append((tag + " " + nm, errd(a, r), 3 * tol))
+
+
+@leaves_no_footprint
+def check_masked_pred_head():
+    """functional.MaskedPredLossFn (l2norm twice, the logits GEMM, ce_rows, sum_f32 twice, the two backward GEMMs -- the label-
+    embedding one transA, transB with split-K over the S rows -- l2norm backward twice) against fp64 torch on the device at
+    the row counts of training: the smallest S for each split of the label-embedding gradient (2: S = 1029 with a ragged first
+    K tile; 25: a Base step's 12 805 masked rows; 64, the slab cap: 32 773 rows, which also takes every row kernel of the head
+    past its grid cap of 4 x 8192 rows), F = 768, V = 100 (the 128-wide kernel's split policy, ldd = 104), V = 500 (ldd = 504),
+    V = 1000, and the floor (5, 2, 8); then skewed labels, labels outside [0, V), zero rows, the paths without a gradient, and
+    target_glu.  Inputs are a table and projections scattered around their label's row, so that the fp64 reference counts 40
+    to 90 % of the rows correct (asserted per case) and `correct` is compared row by row.
+    Tolerances: TOL32 / TOLBF on the tensor scale, three times that for gradients, as check_loss.  An emulation of the bf16 path
+    on the CPU (stored bf16 pn, en, dlogits; fp32 accumulation) lies within 1.1e-2 (dproj) and 8.7e-3 (demb) of fp64 at all of
+    these shapes, about a sixth of the 6e-2 allowed.
+    (gemm_split_range gives every slab ceil(tiles / split) K tiles, so at split 25 and 64 the last slabs hold no tile and are
+    all zero: a reduction that drops the LAST slab shows in demb at split 2, 4 and 24 only, one that drops the first at all.)"""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    cases = [  # S, V, F, sigma, split asserted on the full grid
+        (1029, 504, 256, 5.0, 2), (12805, 504, 256, 5.0, 25), (LOSS_ROWS, 504, 256, 5.0, 64), (2053, 504, 768, 8.0, 4),
+        (1500, 100, 256, 5.0, None), (1029, 500, 256, 5.0, None), (1029, 1000, 256, 4.0, None), (5, 2, 8, 8.0, None)]   # the floor: 3 of its 5 rows correct
+    S, V, Fd = 1029, 504, 256
+    for dtype in (f32, bf):
+        tol = tol_for(dtype)
+        plain = None
+        for (s_, v_, f_, sigma, want) in cases:
+            r = mp_compare(out, "", s_, v_, f_, dtype, sigma=sigma, want_split=want)
+            plain = plain or r   # (1029, 504, 256): the shape of everything below
+        # skewed labels: label 7 on 60 % of the rows, the labels 304 .. 503 on none; the gradient of a label that never occurs
+        # is the pure softmax term, a hundredth of row 7's, so those rows are also compared on their own scale
+        n7 = (3 * S + 4) // 5
+        rest = torch.randperm(304, generator=torch.Generator().manual_seed(4)).repeat(2)[:S - n7]
+        labels = torch.cat([torch.full((n7,), 7), rest])[torch.randperm(S, generator=torch.Generator().manual_seed(5))]
+        cnt = torch.bincount(labels, minlength=V)
+        r = mp_compare(out, "skewed labels ", S, V, Fd, dtype, labels=labels)
+        out.append((r["tag"] + f" premise: label 7 on {int(cnt[7])} rows (>= 60 %), {int((cnt == 0).sum())} of {V} labels never occur (200)",
+                    0.0 if cnt[7] >= 0.6 * S and int((cnt == 0).sum()) == 200 else 1.0, 0.0))
+        never = (cnt == 0).to(DEV)
+        out.append((r["tag"] + " demb on the labels that never occur, on their own scale", errd(r["demb"][never], r["ge"][never]), 3 * tol))
+        # labels outside [0, V): NaN loss, a zero gradient row, and the other rows' gradients as if those rows were not there
+        mp_compare(out, "labels -1, V, V + 1000 ", S, V, Fd, dtype, bad={3: -1, 500: V, S - 1: V + 1000})
+        # the max(||x||, eps) clamp: a zero proj row (all its logits 0: a tie, counted as correct by both) and a zero emb row
+        r = mp_compare(out, "zero rows ", S, V, Fd, dtype, zero_p=11, zero_e=5)
+        fin = all(bool(torch.isfinite(r[k]).all()) for k in ("loss", "dproj", "demb"))
+        out.append((r["tag"] + " loss and gradients finite", 0.0 if fin else 1.0, 0.0))
+        # without a gradient: the same two numbers, bit for bit; no rows: zeros
+        r = plain
+        with torch.no_grad():
+            loss0, nc0 = F.MaskedPredLossFn.apply(r["pd"], r["ed"], r["t32"], MP_TEMP, False)
+        out.append((r["tag"] + " need_grad=False: loss, bit for bit", same_bits(loss0, r["loss"].detach()), 0.0))
+        out.append((r["tag"] + " need_grad=False: n_correct, bit for bit", same_bits(nc0, r["nc"]), 0.0))
+        pe = torch.empty((0, Fd), dtype=dtype, device=DEV, requires_grad=True)
+        eg = r["ed"].clone().requires_grad_(True)
+        lz, nz = F.MaskedPredLossFn.apply(pe, eg, torch.empty(0, dtype=torch.int32, device=DEV), MP_TEMP, True)
+        gz = torch.autograd.grad((lz * MP_GRAD).sum(), (pe, eg))
+        tag = f"masked_pred_head[{'fp32' if dtype == f32 else 'bf16'}] S=0 V={V} F={Fd}"
+        out.append((tag + " loss and n_correct are zero", float(lz.abs().sum().item() + nz.abs().sum().item()), 0.0))
+        ok = gz[0].shape == pe.shape and gz[1].shape == eg.shape and gz[0].dtype == dtype and gz[1].dtype == dtype
+        out.append((tag + " gradients have the inputs' shapes and dtype", 0.0 if ok else 1.0, 0.0))
+        out.append((tag + " demb (non-zero elements)", float((gz[1] != 0).sum().item()), 0.0))
+        mp_glu_case(out, dtype)
+    return out
+
+
+@leaves_no_footprint
+def check_loss_rows_capped():
+    """every other entry point of loss.hip at the smallest size past its grid cap plus a ragged tail (the constants above
+    name the caps), element by element against fp64 torch on the device: the second sweep of each grid-stride loop and the
+    row * ld index arithmetic on it.  l2norm rows carry scales 1 .. 7 with a period that does not divide 32 768, so that a row
+    of the second sweep which reads another row's inverse norm is off by a factor; the all-equal logit row, the repeated
+    positive, the empty CSR rows and the tails of the two reductions lie past the cap on purpose.
+    Tolerances: tol_for(dtype) for stored tensors, TOL32 for fp32 rows and sums."""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    nan, inf = float("nan"), float("inf")
+    rows, first2 = LOSS_ROWS, 4 * LOSS_ROW_BLOCKS
+    ar = torch.arange(rows, device=DEV)
+    past = ar >= first2
+    dn = {f32: "fp32", bf: "bf16"}
+    # ---- l2norm_fwd / l2norm_bwd: D = 256 (four full 64-column passes), D = 100 (lanes 36 .. 63 idle in the second pass)
+    for D in (256, 100):
+        raw, draw = dgen(rows, D, seed=1) * (1 + ar % 7)[:, None], dgen(rows, D, seed=2)
+        for ti, to in ((f32, f32), (bf, bf), (f32, bf)):
+            tag = f"loss_rows_capped l2norm[{dn[ti]} -> {dn[to]}] {rows}x{D}"
+            x = q(raw, ti)
+            x64 = x.double().requires_grad_(True)
+            yr = TF.normalize(x64, dim=-1, eps=1e-8)
+            y, inv = ops.l2norm_fwd(x.to(ti), to)
+            out.append((tag + " y", errd(y, yr), tol_for(to)))
+            out.append((tag + " inv_norm", errd(inv, 1.0 / x64.detach().norm(dim=-1).clamp_min(1e-8)), TOL32))
+            dy = q(draw, to)
+            (dxr,) = torch.autograd.grad(yr, x64, dy.double())
+            dx = ops.l2norm_bwd(dy.to(to), y, inv, ti)
+            tb = TOLBF if bf in (ti, to) else TOL32
+            out.append((tag + " dx", errd(dx, dxr), tb))
+            out.append((tag + f" dx, the rows from {first2} on their own", errd(dx[past], dxr[past]), tb))
+    # ---- ce_rows: 101 columns (two 64-lane passes) in rows of 104, NaN in the pads, -inf in a tenth of the non-target columns,
+    # the target raised on every other row (so that half the rows are correct), an all-equal row in the second sweep
+    S, V, ld = rows, 101, 104
+    gi = torch.Generator(device=DEV).manual_seed(620)
+    lgt = torch.full((S, ld), nan, device=DEV)
+    lgt[:, :V] = 4.0 * torch.randn(S, V, generator=gi, device=DEV)
+    tgt = torch.randint(0, V, (S,), generator=gi, device=DEV)
+    minf = torch.rand(S, V, generator=gi, device=DEV) < 0.1
+    minf[ar, tgt] = False
+    lgt[:, :V].masked_fill_(minf, -inf)
+    lgt[ar, tgt] = torch.where(ar % 2 == 1, lgt[:, :V].max(-1).values + 1.0, lgt[ar, tgt])
+    flat_row = first2 + 2
+    lgt[flat_row, :V] = 1.25
+    l64 = lgt[:, :V].double().requires_grad_(True)
+    rows_ref = TF.cross_entropy(l64, tgt, reduction="none")
+    (dref,) = torch.autograd.grad(rows_ref.sum() * 1.7, l64)
+    mx = l64.detach().max(-1).values
+    hit = l64.detach()[ar, tgt] >= mx
+    all_equal = l64.detach().min(-1).values == mx
+    out.append((f"loss_rows_capped ce_rows premise: {int(hit.sum())} of {S} rows correct (40 to 60 %), one all-equal row, at {flat_row}",
+                0.0 if 0.4 * S <= int(hit.sum()) <= 0.6 * S and int(all_equal.sum()) == 1 and bool(all_equal[flat_row]) else 1.0, 0.0))
+    for ddt in (f32, bf):
+        tag = f"loss_rows_capped ce_rows {S}x{V} ld={ld} dlogits[{dn[ddt]}]"
+        dlog = torch.full((S, ld), nan, dtype=ddt, device=DEV)
+        for flat in (False, True):
+            lrows, corr = ops.ce_rows(lgt, tgt.to(torch.int32), V, ld, dlog, ld, 1.7, flat_wrong=flat)
+            cref = hit & ~all_equal if flat else hit
+            out.append((tag + f" flat_wrong={flat}: correct rows (mismatches)", float((corr.bool() != cref).sum().item()), 0.0))
+            out.append((tag + f" flat_wrong={flat}: loss rows", errd(lrows, rows_ref), TOL32))
+        out.append((tag + " dlogits", errd(dlog[:, :V], dref), tol_for(ddt)))
+        out.append((tag + " pad columns (non-zero elements)", float((dlog[:, V:] != 0).sum().item()), 0.0))
+    # ---- gather_dot: 3 columns (the row itself, two draws); in the second sweep, the positive's own row among the negatives
+    # and another row of y with the positive's content
+    S, N, D = rows, 3, 64
+    idx = torch.randint(0, S, (S, N), generator=gi, device=DEV)
+    idx[:, 0] = ar
+    own, twin = first2 + 2, first2 + 3
+    idx[own, 2] = own
+    idx[twin, 1] = 100
+    i32 = idx.to(torch.int32)
+    for dtype in (f32, bf):
+        tag = f"loss_rows_capped gather_dot[{dn[dtype]}] S={S} N={N} D={D}"
+        X, Y = q(dgen(S, D, seed=11), dtype), q(dgen(S, D, seed=12), dtype)
+        Y[100] = Y[twin]
+        ref = 10.0 * (X.double()[:, None, :] * Y.double()[idx]).sum(-1)
+        mref = torch.zeros((S, N), dtype=torch.bool, device=DEV)
+        mref[:, 1:] = (Y[idx[:, 1:]] == Y[idx[:, :1]]).all(-1)
+        Xd, Yd = X.to(dtype), Y.to(dtype)
+        lg0 = ops.gather_dot(Xd, Yd, i32, 10.0)
+        lg1 = ops.gather_dot(Xd, Yd, i32, 10.0, mask_raw=Yd)
+        mdev = torch.isinf(lg1) & (lg1 < 0)
+        out.append((tag + " without mask_raw", errd(lg0, ref), TOL32))
+        out.append((tag + f" premise: the reference masks ({own}, 2) and ({twin}, 1)", 0.0 if bool(mref[own, 2]) and bool(mref[twin, 1]) else 1.0, 0.0))
+        out.append((tag + f" with mask_raw: -inf placement ({int(mref.sum())} masked in the reference; differing positions)", float((mref != mdev).sum().item()), 0.0))
+        out.append((tag + " with mask_raw: the other logits", errd(torch.where(mdev, torch.zeros_like(lg1), lg1), torch.where(mref, torch.zeros_like(ref), ref)), TOL32))
+    # ---- rows_wsum: a CSR with row % 4 entries per row (rows 32 768 and 32 772 are empty), every operand / result dtype pair
+    D, R = 64, 1000
+    cnt = ar % 4
+    off = torch.zeros(rows + 1, dtype=torch.int32, device=DEV)
+    off[1:] = torch.cumsum(cnt, 0).to(torch.int32)
+    E = int(off[-1].item())
+    src = torch.randint(0, R, (E,), generator=gi, device=DEV).to(torch.int32)
+    w = dgen(E, seed=22)
+    rowid = torch.repeat_interleave(ar, cnt)
+    empty_past = past & (cnt == 0)
+    for ydt, odt in ((f32, f32), (bf, bf), (bf, f32), (f32, bf)):
+        tag = f"loss_rows_capped rows_wsum[{dn[ydt]} -> {dn[odt]}] {rows}x{D}"
+        Y = q(dgen(R, D, seed=21), ydt)
+        ref = torch.zeros((rows, D), dtype=torch.float64, device=DEV).index_add_(0, rowid, w.double()[:, None] * Y.double()[src.long()])
+        o = torch.full((rows, D), nan, dtype=odt, device=DEV)
+        ops.rows_wsum(Y.to(ydt), src, w, off, rows, out=o, accumulate=False)
+        out.append((tag + " fresh", errd(o, ref), tol_for(odt)))
+        out.append((tag + f" fresh: the {int(empty_past.sum())} empty rows from {first2} (non-zero elements)", float((o[empty_past] != 0).sum().item()), 0.0))
+        o0 = q(dgen(rows, D, seed=23), odt)
+        o = o0.to(odt).clone()
+        ops.rows_wsum(Y.to(ydt), src, w, off, rows, out=o, accumulate=True)
+        out.append((tag + " accumulated", errd(o, o0.double() + ref), tol_for(odt)))
+    # ---- glu_fwd / glu_bwd: one row per block; F = 48 (one partly filled 256-column pass), F = 300 (the second pass ragged)
+    for dtype in (f32, bf):
+        tol = tol_for(dtype)
+        for Fh in (48, 300):
+            x, dy = q(2.0 * dgen(GLU_ROWS, 2 * Fh, seed=31), dtype), q(dgen(GLU_ROWS, Fh, seed=32), dtype)
+            for gate, g in GLU_GATE_REFS.items():
+                xr = x.double().requires_grad_(True)
+                yr = xr[:, :Fh] * g(xr[:, Fh:])
+                (dxr,) = torch.autograd.grad(yr, xr, dy.double())
+                tag = f"loss_rows_capped glu[{dn[dtype]}] {gate} {GLU_ROWS}x{Fh}"
+                out.append((tag + " fwd", errd(ops.glu_fwd(x.to(dtype), gate), yr), tol))
+                out.append((tag + " bwd", errd(ops.glu_bwd(x.to(dtype), dy.to(dtype), gate), dxr), tol))
+        # ---- act_fwd / act_bwd: 256 elements per block
+        x, dy = q(2.0 * dgen(ACT_N, seed=41), dtype), q(dgen(ACT_N, seed=42), dtype)
+        for kind, f in ACT_REFS.items():
+            xr = x.double().requires_grad_(True)
+            yr = f(xr)
+            (dxr,) = torch.autograd.grad(yr, xr, dy.double())
+            tag = f"loss_rows_capped act[{dn[dtype]}] {kind} n={ACT_N}"
+            out.append((tag + " fwd", errd(ops.act_fwd(x.to(dtype), kind), yr), tol))
+            out.append((tag + " bwd", errd(ops.act_bwd(x.to(dtype), dy.to(dtype), kind), dxr), tol))
+    # ---- sum_f32: mean 1, so that a dropped sweep shows; the five elements of the ragged ninth sweep weigh 5 / n = 2.4e-6 of
+    # the sum at that mean, below TOL32, so a second sum carries 1000 on each of them (2.4e-3 of the sum)
+    n = RED_N
+    x = 1.0 + dgen(n, seed=51)
+    out.append((f"loss_rows_capped sum_f32 n={n}", errd(ops.sum_f32(x), x.double().sum().reshape(1)), TOL32))
+    x[-5:] += 1000.0
+    out.append((f"loss_rows_capped sum_f32 n={n}, 1000 on each of the last five", errd(ops.sum_f32(x), x.double().sum().reshape(1)), TOL32))
+    # ---- bce_logits: the last five elements are classified correctly by construction, so that the exact count sees the tail
+    lg = 2.0 * dgen(n, seed=52)
+    t = torch.rand(n, generator=gi, device=DEV) < 0.3
+    t[-5:] = lg[-5:] >= 0
+    l64 = lg.double()
+    gscale = 0.37
+    res, dl = ops.bce_logits(lg, t.to(torch.uint8), gscale, want_grad=True)
+    res0, dl0 = ops.bce_logits(lg, t.to(torch.uint8), gscale, want_grad=False)
+    count = int(((l64 >= 0) == t).sum().item())
+    tag = f"loss_rows_capped bce_logits n={n}"
+    out.append((tag + " mean loss", errd(res[0:1], TF.binary_cross_entropy_with_logits(l64, t.double()).reshape(1)), TOL32))
+    out.append((tag + f" accuracy x n against the fp64 count {count}", float(abs(round(res[1].item() * n) - count)), 0.0))
+    out.append((tag + " dlogits", errd(dl, gscale * (torch.sigmoid(l64) - t.double())), TOL32))
+    out.append((tag + " want_grad=False: no dlogits, the same loss and accuracy bit for bit", 0.0 if dl0 is None else 1.0, 0.0))
+    out.append((tag + " want_grad=False: loss and accuracy", same_bits(res0, res), 0.0))
+    return out
+
+
 GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
     "conv_ln_block_wide": check_conv_ln_block_wide, "convstack": check_convstack, "convstack_wide": check_convstack_wide, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
     "linear_ffn": check_linear_ffn, "activations": check_activations, "loss": check_loss, "adam": check_adam, "dropout_exact": check_dropout_exact,
     "gumbel_vq": check_gumbel_vq, "sampled_negatives": check_sampled_negatives,
     "layernorm_rows": check_layernorm_rows, "layernorm_dropout_ref": check_layernorm_dropout_ref, "colsum_rows": check_colsum_rows,
-    "flat_strided": check_flat_strided,
+    "flat_strided": check_flat_strided, "masked_pred_head": check_masked_pred_head, "loss_rows_capped": check_loss_rows_capped,
 }
 
 if __name__ == "__main__":
