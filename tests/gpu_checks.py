@@ -29,6 +29,29 @@ and two groups run them there, against fp64 torch on the device:
   loss_rows_capped       32 773 rows (4 x 8192 + 5) for l2norm (D = 256, 100), ce_rows (V = 101, ld = 104), gather_dot (N = 3, D = 64)
                          and rows_wsum (D = 64); 8195 rows (8192 + 3) for glu (F = 48, 300); n = 8192 x 256 + 7 for act; n = 1024 x
                          2048 + 5 for sum_f32 and bce_logits
+
+The convolutional position embedding (posconv.hip, posconv_direct.hip; PosConvFn) has three groups at its launch geometry, against
+posconv_ref64 -- a loop over the K taps of a grouped matrix product in fp64 on the device, autograd for the gradients; tests/
+test_posconv_ref.py holds its CPU side.  The constants a retune would move: posconv_dw_kernel's frame chunk TCH = 256 (Cg = 48) /
+128 (Cg = 64) and batch splits BS = 4 / 2 (PDW_TCH, PDW_BS below); posconv_direct_kernel's candidate frame tiles 768, 512, 384 /
+512, 384 (PCD_TILES); pc_group_major_kernel's grid cap of 8192 x 256 chunks of 8 elements (GM_CAP):
+  posconv_batch          bf16, K = 128, G = 16; (B, T) = (5, 300) at Cg = 48: bchunk 2, splits of 2, 2, 1, 0 batches, two chunks with
+                         a 44-frame tail; (8, 257): four full splits, a one-frame tail; (9, 64): bchunk 3, one chunk per batch; at
+                         Cg = 64 (3, 200): splits of 2, 1, two chunks of 128; (5, 129): splits of 3, 2, a one-frame tail.  Where a
+                         tail exists, once more with dy zero outside it.  At (5, 300) the inference forward, x without gradient, a
+                         non-contiguous dy
+  posconv_frames         bf16, K = 128, Cg = 48 as D = 96, G = 2 and Cg = 64 as D = 256, G = 4 (the smallest G with the direct dw
+                         kernel), B = 1: T = 1, 16, 63, 127, 383, 384 (tile 384), 385, 512 (tile 512), 513 (768 against 2 x 384: the
+                         tie goes to the larger tile), 768, 769 (2 x 512; also B = 2), 1153 (2 x 768 on a three-way tie), 1537
+                         (5 x 384) at Cg = 48; T = 1, 65, 384, 385, 512, 513 (2 x 384; also B = 2), 1024 (2 x 512), 1025 (3 x 384),
+                         1537 (5 x 384) at Cg = 64
+  posconv_layouts        group_major at 5 x 16 x 3327 x 8 = 2 129 280 chunks (B = 5, T = 3200, D = 1024, G = 16, left_pad 64; the cap
+                         is 2 097 152) into NaN-filled memory, and at B = T = 1; posconv_weight_fwd's norm and both images at (D, Cg,
+                         K) = (96, 48, 128), (256, 64, 128) in layouts 0 and 1 and (64, 16, 15) in layout 0, placed by the index maps
+                         of posconv.hip's comments, for fp32 -> bf16, bf16 -> bf16, fp32 -> fp32; posconv_weight_bwd on seeded slabs,
+                         nsplit 1 and 4, at (96, 48, 128) and (1024, 64, 128); PosConvFn's GEMM form at (B, T, D, G) = (2, 49, 64, 4)
+                         with K = 15, 3 (odd: the left pad of the gradient copy is K - 1 - K // 2) and 16; the refusals
+Bounds: check_posconv's (tol_for(dtype) for y, x 2 for dx and dbias, x 3 for dv and dg; 1e-2 between the direct and the GEMM form).
 """
 import math
 import sys
@@ -2848,6 +2871,330 @@ def check_loss_rows_capped():
     return out
 
 
+# ------------------------------------------------------------------------ pos_conv at batch geometry (module docstring)
+PCD_TILES = {48: (768, 512, 384), 64: (512, 384)}   # candidate frame tiles of posconv_direct_kernel (64 MT), larger first
+PDW_TCH = {48: 256, 64: 128}                        # frames per chunk of posconv_dw_kernel
+PDW_BS = {48: 4, 64: 2}                             # batch splits (fp32 slabs) of posconv_dw_kernel
+GM_CAP = 8192 * 256                                 # 8-element chunks one sweep of pc_group_major_kernel's grid covers
+
+
+def posconv_direct_tile(Cg, T):
+    """(frames per workgroup, segments) wavlm_posconv_direct launches at T frames: the candidate tile that pads T the least,
+    the larger one on a tie (min() keeps the first of equals)"""
+    bm = min(PCD_TILES[Cg], key=lambda m: -(-T // m) * m)
+    return bm, -(-T // bm)
+
+
+def posconv_dw_geometry(Cg, B, T):
+    """(bchunk, batches per split, chunks per batch, frames in the last chunk) of posconv_dw_kernel"""
+    BS, TCH = PDW_BS[Cg], PDW_TCH[Cg]
+    bchunk = -(-B // BS)
+    per = tuple(max(0, min(B, (s + 1) * bchunk) - s * bchunk) for s in range(BS))
+    nch = -(-T // TCH)
+    return bchunk, per, nch, T - (nch - 1) * TCH
+
+
+def posconv_ref64(x, v, g, bias, G):
+    """x + gelu(conv1d(x, g v / ||v||, padding K // 2, groups G) + bias)[:, :T] as a loop over the K taps of a grouped
+    matrix product on the zero-padded x -- the reference's SamePad for odd and even K.  Shares nothing with the code under
+    test and asks no convolution of the vendor library; autograd differentiates it."""
+    B, T, D = x.shape
+    Cg, K = v.shape[1], v.shape[2]
+    P = K // 2
+    w = (g.view(1, 1, K) * v / v.norm(dim=(0, 1), keepdim=True)).view(G, Cg, Cg, K)   # [group, column, channel, tap]
+    xp = TF.pad(x, (0, 0, P, P)).view(B, T + 2 * P, G, Cg)
+    L = T + 2 * P - K + 1          # frames the padded convolution gives: T + 1 for even K, T for odd
+    u = x.new_zeros(B, L, G, Cg)
+    for k in range(K):
+        u = u + torch.einsum("btgc,gnc->btgn", xp[:, k:k + L], w[..., k])
+    return x + TF.gelu(u.reshape(B, L, D)[:, :T] + bias)
+
+
+def pc_inputs(B, T, D, K, G, dtype):
+    """check_posconv's distributions, drawn on the device and rounded through dtype: x, v, g, bias, dy"""
+    Cg = D // G
+    x = q(dgen(B, T, D, seed=1), dtype)
+    v = q(dgen(D, Cg, K, seed=2, scale=math.sqrt(4.0 / (K * D))), dtype)
+    g = q(v.norm(dim=(0, 1), keepdim=True) * (1 + 0.1 * dgen(1, 1, K, seed=3)), dtype)
+    bias = q(0.1 * dgen(D, seed=4), dtype)
+    dy = q(dgen(B, T, D, seed=5), dtype)
+    return x, v, g, bias, dy
+
+
+def pc_ref(inp, G, more_dy=()):
+    """(y, [(dx, dv, dg, dbias) for inp's dy and every further dy]) in fp64 on the device"""
+    x, v, g, bias, dy = inp
+    leaves = [t.double().requires_grad_(True) for t in (x, v, g, bias)]
+    y = posconv_ref64(*leaves, G)
+    return y.detach(), [torch.autograd.grad(y, leaves, d.double(), retain_graph=True) for d in (dy,) + tuple(more_dy)]
+
+
+def pc_device(inp, G, dtype, dy=None, x_grad=True, direct=True):
+    """PosConvFn forward and backward on copies of the inputs in dtype -> (y, (dx, dv, dg, dbias))"""
+    x, v, g, bias, dy0 = inp
+    xd = x.to(dtype, copy=True).requires_grad_(x_grad)
+    vd, gd, bd = [t.to(dtype, copy=True).requires_grad_(True) for t in (v, g, bias)]
+    old = F.POSCONV_DIRECT
+    F.POSCONV_DIRECT = old and direct
+    try:
+        yd = F.PosConvFn.apply(xd, vd, gd, bd, G)
+        yd.backward(dy0.to(dtype) if dy is None else dy)
+    finally:
+        F.POSCONV_DIRECT = old
+    return yd.detach(), (xd.grad, vd.grad, gd.grad, bd.grad)
+
+
+def pc_lines(out, tag, got, ref, tol, names=("dx", "dv", "dg", "dbias")):
+    """check_posconv's bounds: y at tol, dx and dbias at twice, dv and dg at three times that"""
+    (y, grads), (yr, gr) = got, ref
+    if y is not None:
+        out.append((tag + " y", errd(y, yr), tol))
+    for nm, a, b in zip(("dx", "dv", "dg", "dbias"), grads, gr):
+        if nm in names:
+            out.append((f"{tag} {nm}", errd(a, b) if a is not None else float("inf"), tol * (3 if nm in ("dv", "dg") else 2)))
+
+
+def pc_direct_case(out, tag, B, T, D, G, dtype=torch.bfloat16, K=128, more_dy=None):
+    """one shape on the direct kernels: the five outputs against fp64, and against the GEMM form on the same inputs.
+    more_dy(inputs) names further output gradients for the one reference graph.  Returns (inputs, (y, gradient sets), device run)"""
+    inp = pc_inputs(B, T, D, K, G, dtype)
+    ref = pc_ref(inp, G, more_dy(inp) if more_dy else ())
+    got = pc_device(inp, G, dtype)
+    pc_lines(out, tag, got, (ref[0], ref[1][0]), tol_for(dtype))
+    alt = pc_device(inp, G, dtype, direct=False)
+    for nm, a, b in (("y", got[0], alt[0]), ("dx", got[1][0], alt[1][0]), ("dv", got[1][1], alt[1][1])):
+        out.append((f"{tag} direct vs gemm {nm}", errd(a, b), 1.0e-2))
+    return inp, ref, got
+
+
+def pc_tail_dy(dy, first):
+    """dy with the frames before `first` zeroed"""
+    d = dy.clone()
+    d[:, :first] = 0
+    return d
+
+
+def pc_direct_premise(Cg, G, T, K=128):
+    ok = F.POSCONV_DIRECT and ops.posconv_direct_supported(torch.bfloat16, Cg, K, T) and ops._lib.lib().wavlm_posconv_dw_direct_splits(Cg, G) > 0
+    return 0.0 if ok else 1.0
+
+
+# Cg, D, B, T and what posconv_dw_kernel makes of them: bchunk, batches per split, chunks per batch, frames in the last chunk
+PC_BATCH_CASES = [
+    (48, 768, 5, 300, 2, (2, 2, 1, 0), 2, 44),     # a partial and an empty split; a 44-frame tail chunk
+    (48, 768, 8, 257, 2, (2, 2, 2, 2), 2, 1),      # all four splits full; a tail chunk of one frame
+    (48, 768, 9, 64, 3, (3, 3, 3, 0), 1, 64),      # three batches per workgroup, one chunk each
+    (64, 1024, 3, 200, 2, (2, 1), 2, 72),          # TCH = 128: two chunks per batch
+    (64, 1024, 5, 129, 3, (3, 2), 2, 1),           # a tail chunk of one frame
+]
+
+
+@leaves_no_footprint
+def check_posconv_batch():
+    """PosConvFn on the direct kernels (bf16, K = 128, G = 16) where a workgroup of posconv_dw_kernel walks several batches:
+    `bb` advances, a split is partial or empty, and the register stage crosses from one batch's last chunk to the next
+    batch's first.  Reference: posconv_ref64.  A one-frame tail chunk is 1 / 257 of a weight gradient's terms, about the
+    size of the dv bound, so the shapes with a tail also run a backward whose dy is zero outside the last chunk: there a lost
+    chunk is the whole gradient.  At (5, 300): the inference forward, a backward without dx, a non-contiguous dy."""
+    out = []
+    dtype, G = torch.bfloat16, 16
+    tol = tol_for(dtype)
+    for i, (Cg, D, B, T, bchunk, per, nch, tail) in enumerate(PC_BATCH_CASES):
+        tag = f"posconv_batch Cg={Cg} B={B} T={T}"
+        out.append((tag + " premise: the direct kernels take it", pc_direct_premise(Cg, G, T), 0.0))
+        out.append((tag + f" premise: bchunk {bchunk}, splits of {per} batches, {nch} chunk(s), {tail} frame(s) in the last",
+                    0.0 if posconv_dw_geometry(Cg, B, T) == (bchunk, per, nch, tail) else 1.0, 0.0))
+        first = (nch - 1) * PDW_TCH[Cg]   # first frame of the last chunk
+        inp, (yr, sets), got = pc_direct_case(out, tag, B, T, D, G, more_dy=(lambda I: [pc_tail_dy(I[4], first)]) if nch > 1 else None)
+        if nch > 1:
+            gt = pc_device(inp, G, dtype, dy=pc_tail_dy(inp[4], first).to(dtype))
+            pc_lines(out, tag + f", dy zero outside the last {tail} frame(s):", (None, gt[1]), (yr, sets[1]), tol)
+        if i == 0:
+            with torch.no_grad():
+                yi = F.infer_apply(F.PosConvFn, *[t.to(dtype) for t in inp[:4]], G)
+            out.append((tag + " inference forward (no pre-activation kept) == training forward, bit for bit", same_bits(yi, got[0]), 0.0))
+            gn = pc_device(inp, G, dtype, x_grad=False)
+            out.append((tag + " x.requires_grad == False: dx is None", 0.0 if gn[1][0] is None else 1.0, 0.0))
+            pc_lines(out, tag + " x.requires_grad == False:", (None, gn[1]), (yr, sets[0]), tol, names=("dv", "dg", "dbias"))
+            dync = inp[4].to(dtype).transpose(0, 1).contiguous().transpose(0, 1)
+            out.append((tag + " premise: that dy is not contiguous", 0.0 if not dync.is_contiguous() else 1.0, 0.0))
+            gc = pc_device(inp, G, dtype, dy=dync)
+            pc_lines(out, tag + " non-contiguous dy:", (None, gc[1]), (yr, sets[0]), tol)
+    return out
+
+
+# T -> (frame tile, segments) that posconv_direct_tile is meant to give, per group width; (D, G) are the smallest with the
+# direct weight-gradient kernel
+PC_FRAME_DG = {48: (96, 2), 64: (256, 4)}
+PC_FRAME_CASES = {
+    48: [(1, 384, 1), (16, 384, 1), (63, 384, 1), (127, 384, 1),       # T < K: the window is mostly padding
+         (383, 384, 1), (384, 384, 1),                                 # the smallest tile, one short and exact
+         (385, 512, 1), (512, 512, 1),                                 # the middle tile
+         (513, 768, 1),                                                # 768 = 2 x 384 padded frames: the tie goes to the larger tile
+         (768, 768, 1), (769, 512, 2),                                 # exact, and one past: two segments of 512
+         (1153, 768, 2),                                               # 1536 padded frames with every tile: the larger one
+         (1537, 384, 5)],                                              # five segments, one frame in the last
+    64: [(1, 384, 1), (65, 384, 1), (384, 384, 1), (385, 512, 1), (512, 512, 1),
+         (513, 384, 2),                                                # 768 against 1024 padded frames
+         (1024, 512, 2),                                               # two exact segments of the larger tile
+         (1025, 384, 3), (1537, 384, 5)],
+}
+PC_FRAME_B2 = {48: 769, 64: 513}   # the multi-segment T that also runs with two batches
+
+
+@leaves_no_footprint
+def check_posconv_frames():
+    """the frame-tile edges of posconv_direct_kernel (and the chunk edges of posconv_dw_kernel under them) at small channel
+    counts, bf16, K = 128: every tile height, the tie-break, exact multiples and one past, T below K, two to five segments"""
+    out = []
+    for Cg, cases in PC_FRAME_CASES.items():
+        D, G = PC_FRAME_DG[Cg]
+        for (T, bm, nseg) in cases:
+            for B in (1, 2) if T == PC_FRAME_B2[Cg] else (1,):
+                tag = f"posconv_frames Cg={Cg} B={B} T={T}"
+                out.append((tag + " premise: the direct kernels take it", pc_direct_premise(Cg, G, T), 0.0))
+                out.append((tag + f" premise: {nseg} segment(s) of {bm} frames", 0.0 if posconv_direct_tile(Cg, T) == (bm, nseg) else 1.0, 0.0))
+                pc_direct_case(out, tag, B, T, D, G)
+    return out
+
+
+def gelu_grad64(a):
+    return 0.5 * (1 + torch.erf(a / math.sqrt(2.0))) + a * torch.exp(-0.5 * a * a) / math.sqrt(2 * math.pi)
+
+
+def pc_group_major_case(out, tag, B, T, D, G, left_pad, Tp, dtype, poison):
+    Cg = D // G
+    x = q(dgen(B, T, D, seed=61), dtype).to(dtype)
+    a = q(2.0 * dgen(B, T, D, seed=62), dtype).to(dtype)
+
+    def placed(t):
+        """the group-major, time-padded image by torch indexing"""
+        o = torch.zeros((B, G, Tp, Cg), dtype=t.dtype, device=DEV)
+        o[:, :, left_pad:left_pad + T] = t.view(B, T, G, Cg).permute(0, 2, 1, 3)
+        return o
+
+    def interior(o):
+        return o[:, :, left_pad:left_pad + T].permute(0, 2, 1, 3).reshape(B, T, D)
+
+    def pads(o):
+        return float((o[:, :, :left_pad] != 0).sum().item() + (o[:, :, left_pad + T:] != 0).sum().item())
+
+    nbytes = B * G * Tp * Cg * x.element_size()
+    if poison:
+        _poison(nbytes)
+    o, nat = ops.group_major(x, None, G, left_pad, Tp)
+    out.append((tag + " plain copy == torch indexing, bit for bit", same_bits(o, placed(x)), 0.0))
+    out.append((tag + " plain copy: pad rows (non-zero elements)", pads(o), 0.0))
+    out.append((tag + " plain copy: no nat unless asked", 0.0 if nat is None else 1.0, 0.0))
+    del o
+    for is_grad, ref in ((False, x.double() * gelu_grad64(a.double())), (True, x.double() * a.double())):
+        sub = tag + (" x * aux" if is_grad else " x * gelu'(aux)")
+        if poison:
+            _poison(nbytes)
+        o, nat = ops.group_major(x, a, G, left_pad, Tp, want_nat=True, aux_is_grad=is_grad)
+        out.append((sub, errd(o, placed(ref)), tol_for(dtype)))
+        out.append((sub + ": pad rows (non-zero elements)", pads(o), 0.0))
+        out.append((sub + ": nat == the interior rows, bit for bit", same_bits(nat, interior(o)), 0.0))
+        del o, nat
+
+
+def pc_image_offsets(Cg, K, layout):
+    """offset inside a group's image of element (column n, tap, channel c), as posconv.hip's pc_weight_kernel states it:
+    layout 0 = [n][tap][c]; layout 1 = [c / 8][(tap % 16) / 4][tap / 16][tap % 4][n][c % 8]"""
+    n = torch.arange(Cg, device=DEV).view(Cg, 1, 1)
+    tap = torch.arange(K, device=DEV).view(1, K, 1)
+    c = torch.arange(Cg, device=DEV).view(1, 1, Cg)
+    if layout == 0:
+        return ((n * K + tap) * Cg + c).reshape(-1)
+    J = K // 16
+    return (((((c // 8 * 4 + tap % 16 // 4) * J + tap // 16) * 4 + tap % 4) * Cg + n) * 8 + c % 8).reshape(-1)
+
+
+def pc_weight_ref(v, g):
+    """fp64: norm [K], w [D, Cg, K]"""
+    norm = v.double().norm(dim=(0, 1))
+    return norm, g.double().view(1, 1, -1) * v.double() / norm
+
+
+def pc_weight_fwd_case(out, D, Cg, K, layout, pdt, odt):
+    dn = {torch.float32: "fp32", torch.bfloat16: "bf16"}
+    tag = f"posconv_layouts weight_fwd[{dn[pdt]} -> {dn[odt]}] D={D} Cg={Cg} K={K} layout {layout}"
+    G = D // Cg
+    v = q(dgen(D, Cg, K, seed=71, scale=math.sqrt(4.0 / (K * D))), pdt)
+    g = q(v.norm(dim=(0, 1)) * (1 + 0.1 * dgen(K, seed=72)), pdt)
+    norm, w = pc_weight_ref(v, g)
+    w = w.view(G, Cg, Cg, K)                                   # [group, column, channel, tap]
+    Ef = w.permute(0, 1, 3, 2)                                 # Wf element (n, tap, c) = w[grp * Cg + n, c, tap]
+    Eb = w.flip(-1).permute(0, 2, 3, 1)                        # Wb element (n, tap, c) = w[grp * Cg + c, n, K - 1 - tap]
+    off = pc_image_offsets(Cg, K, layout)
+    out.append((tag + " premise: the index map is a permutation", 0.0 if torch.equal(off.sort().values, torch.arange(Cg * K * Cg, device=DEV)) else 1.0, 0.0))
+    Wf, Wb, nd = ops.posconv_weight_fwd(v.to(pdt), g.to(pdt), odt, layout=layout)
+    out.append((tag + " norm", errd(nd, norm), TOL32))
+    for nm, W, E in (("Wf", Wf, Ef), ("Wb", Wb, Eb)):
+        ref = torch.empty((G, Cg * K * Cg), dtype=torch.float64, device=DEV)
+        ref[:, off] = E.reshape(G, -1)
+        out.append((f"{tag} {nm}", errd(W.view(G, -1), ref), tol_for(odt)))
+
+
+def pc_weight_bwd_case(out, D, Cg, K, nsplit, pdt):
+    dn = {torch.float32: "fp32", torch.bfloat16: "bf16"}
+    tag = f"posconv_layouts weight_bwd[{dn[pdt]}] D={D} Cg={Cg} K={K} nsplit={nsplit}"
+    G = D // Cg
+    v = q(dgen(D, Cg, K, seed=71, scale=math.sqrt(4.0 / (K * D))), pdt)
+    g = q(v.norm(dim=(0, 1)) * (1 + 0.1 * dgen(K, seed=72)), pdt)
+    slabs = dgen(nsplit, G, Cg, K * Cg, seed=73)               # [split][group][column][(tap, channel)]
+    dw = slabs.double().sum(0).view(G, Cg, K, Cg).permute(0, 1, 3, 2).reshape(D, Cg, K)
+    v64, g64 = v.double().requires_grad_(True), g.double().requires_grad_(True)
+    _, w = pc_weight_ref(v64, g64)
+    dvr, dgr = torch.autograd.grad(w, [v64, g64], dw)
+    norm = v.double().norm(dim=(0, 1)).float()
+    dv, dg = ops.posconv_weight_bwd(slabs, v.to(pdt), g.to(pdt), norm, nsplit=nsplit)
+    out.append((tag + " dv", errd(dv, dvr), 3 * tol_for(pdt)))
+    out.append((tag + " dg", errd(dg, dgr), 3 * tol_for(pdt)))
+
+
+@leaves_no_footprint
+def check_posconv_layouts():
+    """the pc_* kernels of posconv.hip one by one -- group_major past one sweep of its capped grid (into poisoned memory, so
+    that a chunk nobody writes reads as NaN), the two weight images element by element through their index maps, the slab
+    sum of the weight-norm backward on known slabs -- and PosConvFn's GEMM form at odd kernel widths, where the left pad of
+    the gradient copy is K - 1 - K // 2 and not K // 2 - 1."""
+    out = []
+    f32, bf = torch.float32, torch.bfloat16
+    dn = {f32: "fp32", bf: "bf16"}
+    # ---- group_major: 5 x 16 x 3327 x 8 = 2 129 280 chunks, 32 128 past GM_CAP; and the smallest call there is
+    B, T, D, G, lp, Tp = 5, 3200, 1024, 16, 64, 3327
+    chunks = B * G * Tp * (D // G // 8)
+    out.append((f"posconv_layouts group_major premise: {chunks} chunks, between one and two sweeps of {GM_CAP}", 0.0 if GM_CAP < chunks < 2 * GM_CAP else 1.0, 0.0))
+    for dtype in (bf, f32):
+        pc_group_major_case(out, f"posconv_layouts group_major[{dn[dtype]}] above the cap", B, T, D, G, lp, Tp, dtype, True)
+        pc_group_major_case(out, f"posconv_layouts group_major[{dn[dtype]}] B=T=1", 1, 1, 64, 4, 0, 1, dtype, False)
+    x = torch.zeros((1, 4, 48), dtype=bf, device=DEV)
+    out.append(("posconv_layouts group_major refuses Cg = 12 (no multiple of 8)", refused(lambda: ops.group_major(x, None, 4, 0, 4)), 0.0))
+    out.append(("posconv_layouts group_major refuses Tp < left_pad + T", refused(lambda: ops.group_major(x, None, 1, 2, 5)), 0.0))
+    # ---- the weight images and norm
+    for (D, Cg, K, layouts) in ((96, 48, 128, (0, 1)), (256, 64, 128, (0, 1)), (64, 16, 15, (0,))):
+        for layout in layouts:
+            for pdt, odt in ((f32, bf), (bf, bf), (f32, f32)):
+                pc_weight_fwd_case(out, D, Cg, K, layout, pdt, odt)
+    v15 = dgen(64, 16, 15, seed=71)
+    out.append(("posconv_layouts weight_fwd refuses layout 1 at K = 15", refused(lambda: ops.posconv_weight_fwd(v15, v15.norm(dim=(0, 1)), f32, layout=1)), 0.0))
+    # ---- the slab sum and the weight-norm backward
+    for (D, Cg, K) in ((96, 48, 128), (1024, 64, 128)):
+        for nsplit in (1, 4):
+            for pdt in (f32, bf):
+                pc_weight_bwd_case(out, D, Cg, K, nsplit, pdt)
+    # ---- PosConvFn, GEMM form, odd and even K
+    for K in (15, 3, 16):
+        for dtype in (f32, bf):
+            B, T, D, G = 2, 49, 64, 4
+            tag = f"posconv_layouts PosConvFn[{dn[dtype]}] B={B} T={T} D={D} K={K} G={G}"
+            inp = pc_inputs(B, T, D, K, G, dtype)
+            yr, sets = pc_ref(inp, G)
+            pc_lines(out, tag, pc_device(inp, G, dtype), (yr, sets[0]), tol_for(dtype))
+    return out
+
+
 GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
     "conv_ln_block_wide": check_conv_ln_block_wide, "convstack": check_convstack, "convstack_wide": check_convstack_wide, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
@@ -2855,6 +3202,7 @@ GROUPS = {
     "gumbel_vq": check_gumbel_vq, "sampled_negatives": check_sampled_negatives,
     "layernorm_rows": check_layernorm_rows, "layernorm_dropout_ref": check_layernorm_dropout_ref, "colsum_rows": check_colsum_rows,
     "flat_strided": check_flat_strided, "masked_pred_head": check_masked_pred_head, "loss_rows_capped": check_loss_rows_capped,
+    "posconv_batch": check_posconv_batch, "posconv_frames": check_posconv_frames, "posconv_layouts": check_posconv_layouts,
 }
 
 if __name__ == "__main__":

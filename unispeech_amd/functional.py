@@ -781,8 +781,8 @@ FUSE_BIAS_COLSUM = os.environ.get("WAVLM_FUSE_BIAS_COLSUM", "1") != "0"  # fc1 b
 
 class PosConvFn(torch.autograd.Function):
     """out = x + gelu(weight_norm_conv1d(x) + bias)[:, :T]  (WavLM/WavLM.py:514-527, 577-579; SamePad drops the last
-    frame).  G*B overlapping-row GEMMs over a group-major, time-padded copy of x; bias, GELU and the residual add
-    run in the GEMM epilogue."""
+    frame of an even kernel width and none of an odd one).  G*B overlapping-row GEMMs over a group-major, time-padded
+    copy of x; bias, GELU and the residual add run in the GEMM epilogue."""
 
     @staticmethod
     def forward(ctx, x, v, g, bias, groups):
@@ -816,18 +816,21 @@ class PosConvFn(torch.autograd.Function):
         xg, u, Wb, norm, v, g = ctx.saved_tensors
         B, T, D, K, Cg, G, Tp = ctx.dims
         dyc = dy.contiguous()
-        dug, du = ops.group_major(dyc, u, G, K // 2 - 1, Tp, want_nat=True)
+        # dx[t] = sum_k w[k] du[t - k + K // 2] is a correlation of the tap-flipped image Wb[tap] = w[K - 1 - tap] with du padded
+        # by K - 1 - K // 2 rows on the left: K // 2 - 1 for even K, K // 2 for odd (SamePad drops no frame there)
+        P = K - 1 - K // 2
+        dug, du = ops.group_major(dyc, u, G, P, Tp, want_nat=True)
         dbias = ops.colsum(du.view(B * T, D), v.dtype)
         if ctx.direct and ops._lib.lib().wavlm_posconv_dw_direct_splits(Cg, G) > 0:
             # direct form: fp32 partial sums over parts of the batch, added up by the weight-norm backward
-            dWf, nsplit = ops.posconv_dw_direct(xg, dug, K // 2 - 1, T, K)
+            dWf, nsplit = ops.posconv_dw_direct(xg, dug, P, T, K)
         else:
             # weight gradient in the forward GEMM layout, fp32: dWf[g][col][(tap, ci)]
             # computed transposed ([(tap, ci)][col]: M = 6144 rows, N = 48): the 48-wide side sits on the 64-column tile
             # edge (75 % MFMA use) instead of on a 128-row tile edge (37 %) -- 1.26 -> ~0.5 ms at cfg2
             dWfT = torch.empty((G, K * Cg, Cg), dtype=torch.float32, device=dy.device)
             ops.gemm(xg, dug, dWfT, K * Cg, Cg, T, lda=Cg, ldb=Cg, ldc=Cg, transA=True, transB=True,
-                     b_off=(K // 2 - 1) * Cg, KB=B, sA_kb=G * Tp * Cg, sB_kb=G * Tp * Cg, batch=(1, G),
+                     b_off=P * Cg, KB=B, sA_kb=G * Tp * Cg, sB_kb=G * Tp * Cg, batch=(1, G),
                      sA=(0, Tp * Cg), sB=(0, Tp * Cg), sC=(0, Cg * K * Cg))
             dWf, nsplit = dWfT.transpose(1, 2).contiguous(), 1
         dv, dg = ops.posconv_weight_bwd(dWf, v.contiguous(), g.contiguous().view(-1), norm, nsplit=nsplit)
