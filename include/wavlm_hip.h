@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WAVLM_HIP_ABI_VERSION 29
+#define WAVLM_HIP_ABI_VERSION 30
 int wavlm_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -712,6 +712,40 @@ int64_t wavlm_fbank_frames(int64_t len, int32_t S, int32_t P);
 int wavlm_fbank_rows(const void* x, int32_t x_dtype, int64_t x_stride, int32_t B, int64_t L, const int32_t* lengths, int32_t W,
                      int32_t S, int32_t P, int32_t M, const float* window, const float* twiddle, const int32_t* mel_idx,
                      const float* mel_w, int32_t n_mel_w, float* y, int64_t y_stride, int64_t Tmax, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CTC loss, its gradient and the greedy decode (ABI 30, csrc/ctc.hip): the loss of ASR fine-tuning,
+ * src/fairseq/criterions/ctc.py:113-147 -- F.ctc_loss(log_softmax(logits.float(), -1), targets_flat, input_lengths,
+ * target_lengths, blank, reduction="none", zero_infinity) and its gradient with respect to the LOGITS (the log-softmax is
+ * src/fairseq/models/hubert/hubert_asr.py:155-162 get_normalized_probs(log_probs=True) and is fused) -- and the argmax /
+ * unique_consecutive / != blank of ctc.py:200-201.
+ *   logits   fp32 or bf16, element (b, t, c) at b * stride_b + t * stride_t + c (strides in elements, unit class stride): a
+ *            batch-first [B, T, C] tensor and the T x B x C view of one are both read in place; the view must not overlap itself
+ *   targets  int32 [n_targets] flat; sample b's labels are targets[target_offsets[b] .. target_offsets[b + 1]); at most Lmax each
+ *   input_lengths int32 [B] on the device, clamped to [0, T]
+ *   grad_out fp32 [B]: the gradient of whatever follows with respect to each sample's loss (ones for reduction="sum")
+ *   nll      fp32 [B]: the loss per sample; +inf where no alignment exists -- with zero_infinity 0, and that sample's gradient 0;
+ *            NaN (and a zero gradient) where an offset or a label of the sample is out of range
+ *   dlogits  dtype and strides of logits: grad_out[b] * (softmax - posterior); rows t >= input_lengths[b] are zero, and without
+ *            zero_infinity the rows of a sample without an alignment are NaN, as torch's are.  Nothing outside the B x T x C
+ *            view is written.
+ *   workspace  wavlm_ctc_workspace_bytes(B, T, Lmax) bytes, 8-byte aligned: nll and the row log-sum-exp in float64, and
+ *            alpha [B, T, 2 Lmax + 1] in fp32
+ * input_length 0: the loss is 0 for an empty target and +inf otherwise.  Three launches (row log-sum-exp; alpha; beta + gradient),
+ * one workgroup per sample in the last two.  The per-class sums run in a fixed order, no atomics: results are bitwise
+ * reproducible, and a sample's loss and gradient do not depend on B or on where it sits in the batch.
+ * wavlm_ctc_supported (host): 1 for 1 <= C <= 1024 and 0 <= Lmax <= 1023; wavlm_ctc_loss returns -1 otherwise.
+ * wavlm_ctc_greedy: tokens int32 [B, T] (sample b's decode in tokens[b, 0 .. counts[b]), -1 behind it), counts int32 [B]; the
+ * argmax takes the lowest class among equal maxima; any C >= 1.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_ctc_supported(int32_t C, int32_t Lmax);
+uint64_t wavlm_ctc_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
+int wavlm_ctc_loss(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                   const int32_t* targets, const int32_t* target_offsets, int32_t n_targets, int32_t Lmax,
+                   const int32_t* input_lengths, int32_t blank, int32_t zero_infinity, const float* grad_out, float* nll,
+                   void* dlogits, void* workspace, uint64_t ws_bytes, void* stream);
+int wavlm_ctc_greedy(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                     const int32_t* input_lengths, int32_t blank, int32_t* tokens, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

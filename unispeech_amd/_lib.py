@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVLM_HIP_LIB") or os.path.join(_HERE, "lib", "libwavlm_hip.so")
 
 _lib = None
-ABI_VERSION = 29  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
+ABI_VERSION = 30  # include/wavlm_hip.h WAVLM_HIP_ABI_VERSION this binding was written against
 
 F32, BF16, I16 = 0, 1, 2   # csrc/common.hpp WL_F32, WL_BF16, WL_I16 (16-bit PCM: input only)
 
@@ -214,6 +214,11 @@ SIGNATURES = {
     "wavlm_fbank_frames": (c_i64, [c_i64, c_i32, c_i32]),
     "wavlm_fbank_rows": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                  c_vp, c_i64, c_i64, c_vp]),
+    "wavlm_ctc_supported": (c_i32, [c_i32, c_i32]),
+    "wavlm_ctc_workspace_bytes": (c_u64, [c_i32, c_i32, c_i32]),
+    "wavlm_ctc_loss": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp,
+                               c_vp, c_vp, c_vp, c_u64, c_vp]),
+    "wavlm_ctc_greedy": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

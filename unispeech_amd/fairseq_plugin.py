@@ -21,6 +21,10 @@ Registered:
              wav2vec2_mi355x  (Wav2Vec2Model  <- src/fairseq/models/wav2vec/wav2vec2.py:274  @register_model("wav2vec2"))
   criterions wavlm_mi355x, hubert_mi355x  (WavLMCriterion  <- criterions/wavlm_criterion.py:38, hubert_criterion.py:39)
              wav2vec_mi355x  (Wav2vecCriterion  <- criterions/wav2vec_criterion.py:36)
+  fine-tuning  hubert_ctc_mi355x, wav2vec_ctc_mi355x  (ctc.EncoderCtc  <- models/hubert/hubert_asr.py:138 @register_model("hubert_ctc"),
+             models/wav2vec/wav2vec2_asr.py @register_model("wav2vec_ctc"): one class, the checkpoint at `w2v_path` picks the encoder)
+             criterion ctc_mi355x  (ctc.CtcCriterion  <- criterions/ctc.py:65 @register_criterion("ctc"))
+             register(override=True) puts them under `hubert_ctc`, `wav2vec_ctc` and `ctc` as well.
 Tasks (`hubert_pretraining`, `utterance_mixing_pretraining`) are the reference's own: they are the *caller* of this
 path; the sample dict they collate is consumed unchanged.
 
@@ -181,6 +185,78 @@ def _w2v_classes():
     return W2VModel, W2VCriterion, W2VCfg, W2VCritCfg
 
 
+def _ctc_classes():
+    """CTC fine-tuning: EncoderCtc <- hubert_asr.py:138 HubertCtc / wav2vec2_asr.py Wav2VecCtc, CtcCriterion <- criterions/ctc.py:65"""
+    from typing import Any
+    from fairseq.criterions import FairseqCriterion
+    from fairseq.dataclass import FairseqDataclass
+    from fairseq.models import BaseFairseqModel
+    from . import ctc
+    try:
+        from omegaconf import II
+        sentence_avg_default = II("optimization.sentence_avg")
+    except Exception:   # no omegaconf: the field is a plain flag
+        sentence_avg_default = False
+    ref_defaults = {"dropout_input": 0.0, "dropout": 0.0, "attention_dropout": 0.0, "activation_dropout": 0.0, "mask_length": 10,
+                    "mask_prob": 0.5, "mask_selection": "static", "mask_other": 0.0, "no_mask_overlap": False,
+                    "mask_channel_length": 10, "mask_channel_prob": 0.0, "mask_channel_selection": "static",
+                    "mask_channel_other": 0.0, "no_mask_channel_overlap": False, "layerdrop": 0.0}   # hubert_asr.py:31-125
+    fields_ = [("w2v_path", str, field(default="", metadata={"help": "path to the pre-trained model"})),
+               ("no_pretrained_weights", bool, field(default=False)), ("normalize", bool, field(default=False)),
+               ("data", Any, field(default=None)), ("w2v_args", Any, field(default=None))]
+    fields_ += [(n, type(v), field(default=v)) for n, v in ctc.OPTIONS.items()]
+    fields_ += [(n, type(v), field(default=v)) for n, v in ref_defaults.items()]
+    CtcModelCfg = make_dataclass("EncoderCtcMI355XConfig", fields_, bases=(FairseqDataclass,))
+
+    @dataclass
+    class CtcCritCfg(FairseqDataclass):   # criterions/ctc.py:23-62
+        zero_infinity: bool = field(default=False, metadata={"help": "zero inf loss when source length <= target length"})
+        sentence_avg: Any = sentence_avg_default
+        post_process: Optional[str] = field(default="letter", metadata={"help": "letter or none"})
+        wer_kenlm_model: Optional[str] = field(default=None, metadata={"help": "refused: the KenLM decoder is not built"})
+        wer_lexicon: Optional[str] = field(default=None, metadata={"help": "refused: the KenLM decoder is not built"})
+        wer_args: Optional[str] = field(default=None, metadata={"help": "refused: the KenLM decoder is not built"})
+
+    class CtcModel(ctc.EncoderCtc, BaseFairseqModel):
+        @classmethod
+        def build_model(cls, cfg, task):
+            """HubertEncoder.__init__ (hubert_asr.py:238-307): the checkpoint's own model config with the overrides applied"""
+            import torch
+            if getattr(cfg, "w2v_args", None) is not None:
+                raise NotImplementedError("w2v_args: the pre-training config is read from the checkpoint at w2v_path")
+            if getattr(cfg, "no_pretrained_weights", False):
+                raise NotImplementedError("no_pretrained_weights")
+            state = torch.load(cfg.w2v_path, map_location="cpu", weights_only=False)
+            scfg = state.get("cfg") if isinstance(state, dict) else None
+            if scfg is None or "model" not in state:
+                raise NotImplementedError("%s: expected a checkpoint dict with 'cfg' and 'model'" % cfg.w2v_path)
+            mcfg = dict(scfg["model"]) if "model" in scfg else dict(scfg)
+            tnorm = bool(dict(scfg["task"]).get("normalize", False)) if "task" in scfg else bool(mcfg.get("normalize", False))
+            assert bool(cfg.normalize) == tnorm, "fine-tuning needs the data normalization of pre-training (--normalize)"
+            arch = "wav2vec2" if mcfg.get("_name", "wavlm") == "wav2vec2" else "wavlm"
+            if arch == "wav2vec2":
+                from .wav2vec2 import Wav2Vec2Config as Cfg
+            else:
+                Cfg = WavLMPretrainConfig
+            wcfg = Cfg(**{k: v for k, v in mcfg.items() if k in Cfg.__dataclass_fields__})
+            options = {k: getattr(cfg, k) for k in list(ctc.OPTIONS) + list(ctc.OVERRIDES) if hasattr(cfg, k)}
+            return cls.build(wcfg, len(task.target_dictionary), arch=arch, state_dict=state["model"], **options)
+
+    class CtcCrit(ctc.CtcCriterion, FairseqCriterion):
+        def __init__(self, cfg, task):
+            FairseqCriterion.__init__(self, task)
+            pp = None if cfg.post_process in (None, "none") else cfg.post_process
+            ctc.CtcCriterion.__init__(self, task.target_dictionary, bool(cfg.zero_infinity), bool(cfg.sentence_avg), pp,
+                                      wer_kenlm_model=cfg.wer_kenlm_model, wer_lexicon=cfg.wer_lexicon, wer_args=cfg.wer_args)
+
+        @staticmethod
+        def reduce_metrics(logging_outputs) -> None:
+            from fairseq import metrics
+            ctc.CtcCriterion.reduce_metrics(logging_outputs, log_scalar=metrics.log_scalar, log_derived=metrics.log_derived)
+
+    return CtcModel, CtcCrit, CtcModelCfg, CtcCritCfg
+
+
 def _invalidate_on_step(opt):
     from . import functional
     inner = opt.step
@@ -237,6 +313,17 @@ def register(override: bool = False, fp16_as_bf16=None):
             if name in CRITERION_REGISTRY:
                 CRITERION_REGISTRY[name] = Criterion
                 CRITERION_DATACLASS_REGISTRY[name] = CritCfg
+        CtcModel, CtcCrit, CtcModelCfg, CtcCritCfg = _ctc_classes()
+        for name in ("hubert_ctc", "wav2vec_ctc"):
+            if name in MODEL_REGISTRY:
+                MODEL_REGISTRY[name] = CtcModel
+                ARCH_MODEL_REGISTRY[name] = CtcModel
+                ARCH_MODEL_NAME_REGISTRY[name] = name
+                MODEL_DATACLASS_REGISTRY[name] = CtcModelCfg
+                ARCH_CONFIG_REGISTRY.pop(name, None)
+        if "ctc" in CRITERION_REGISTRY:
+            CRITERION_REGISTRY["ctc"] = CtcCrit
+            CRITERION_DATACLASS_REGISTRY["ctc"] = CtcCritCfg
         # the optimizer the Trainer builds in bf16 mode (trainer.py:296-316 `optim.FP16Optimizer.build_optimizer(cfg, params)`)
         # and the data-parallel wrapper it puts around the model (trainer.py:250-261 `models.DistributedFairseqModel(...)`)
         _FusedAdam, FP16Standin, _ = _optim_classes()
@@ -280,6 +367,10 @@ def register(override: bool = False, fp16_as_bf16=None):
         W2VModel, W2VCriterion, W2VCfg, W2VCritCfg = _w2v_classes()
         register_model("wav2vec2_mi355x", dataclass=W2VCfg)(W2VModel)
         register_criterion("wav2vec_mi355x", dataclass=W2VCritCfg)(W2VCriterion)
+        CtcModel, CtcCrit, CtcModelCfg, CtcCritCfg = _ctc_classes()
+        register_model("hubert_ctc_mi355x", dataclass=CtcModelCfg)(CtcModel)
+        register_model("wav2vec_ctc_mi355x", dataclass=CtcModelCfg)(type("Wav2VecCtcMI355X", (CtcModel,), {}))
+        register_criterion("ctc_mi355x", dataclass=CtcCritCfg)(CtcCrit)
         from fairseq.optim import register_optimizer
         FusedAdamMI355X, _, AdamCfg = _optim_classes()
         register_optimizer("adam_mi355x", dataclass=AdamCfg)(FusedAdamMI355X)

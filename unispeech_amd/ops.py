@@ -929,3 +929,73 @@ def diar_estimate(z, S, E):
     check(_lib.lib().wavlm_diar_estimate(ptr(z), dt(z), z.stride(0), z.stride(1), B, T, int(S), int(E), ptr(act), ptr(vec), dt(vec),
                                          stream()), "wavlm_diar_estimate")
     return act, vec
+
+
+# ---------------------------------------------------------------------------------------------- CTC
+def _ctc_view(logits):
+    """(stride_b, stride_t) in elements of a [B, T, C]-indexed view with unit class stride"""
+    if logits.dim() != 3:
+        raise ValueError("logits: expected a [B, T, C] view, got %d dimensions" % logits.dim())
+    if logits.shape[2] > 1 and logits.stride(2) != 1:
+        raise ValueError("logits: the class axis must have unit stride")
+    return logits.stride(0), logits.stride(1)
+
+
+def ctc_supported(C, Lmax):
+    return bool(_lib.lib().wavlm_ctc_supported(int(C), int(Lmax)))
+
+
+def ctc_check_supported(C, Lmax):
+    """NotImplementedError naming the argument that is beyond wavlm_ctc_supported; nothing is launched"""
+    L = _lib.lib()
+    if not L.wavlm_ctc_supported(int(C), 0):
+        raise NotImplementedError("ctc_loss: C = %d classes is beyond the kernel's limit (wavlm_ctc_supported: C <= 1024)" % C)
+    if not L.wavlm_ctc_supported(int(C), int(Lmax)):
+        raise NotImplementedError("ctc_loss: L = %d labels in one target is beyond the kernel's limit (wavlm_ctc_supported: "
+                                  "L <= 1023)" % Lmax)
+
+
+def ctc_loss_fwd_bwd(logits, targets, target_offsets, n_targets, Lmax, input_lengths, blank, grad_out=None,
+                     zero_infinity=False, dlogits=None):
+    """wavlm_ctc_loss.  logits: a [B, T, C]-indexed view, fp32 or bf16, any batch / time strides (a T x B x C tensor is passed
+    as its transpose(0, 1)) -- read in place.  targets int32 [n_targets] flat, target_offsets int32 [B + 1], input_lengths int32
+    [B], all on the device; n_targets and Lmax are host integers.  grad_out fp32 [B] (None: ones).  Returns (nll fp32 [B],
+    dlogits with the dtype, shape and strides of logits).  dlogits (optional): a view with exactly those strides to write into."""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    ctc_check_supported(Cn, Lmax)
+    for name, t, n in (("targets", targets, n_targets), ("target_offsets", target_offsets, B + 1),
+                       ("input_lengths", input_lengths, B)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < n:
+            raise ValueError("%s: expected a contiguous int32 device tensor of at least %d elements" % (name, n))
+    if grad_out is None:
+        grad_out = torch.ones(B, dtype=torch.float32, device=dev)
+    elif grad_out.dtype != torch.float32 or grad_out.numel() != B or not grad_out.is_contiguous():
+        raise ValueError("grad_out: expected a contiguous fp32 tensor of B elements")
+    if dlogits is None:
+        dlogits = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=dev)
+    elif dlogits.shape != logits.shape or dlogits.stride() != logits.stride() or dlogits.dtype != logits.dtype:
+        raise ValueError("dlogits: expected the shape, strides and dtype of logits")
+    nll = torch.empty(B, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    need = L.wavlm_ctc_workspace_bytes(B, T, int(Lmax))
+    ws = workspace(dev, need, "ctc")
+    check(L.wavlm_ctc_loss(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(targets), ptr(target_offsets), int(n_targets),
+                           int(Lmax), ptr(input_lengths), int(blank), int(bool(zero_infinity)), ptr(grad_out), ptr(nll),
+                           ptr(dlogits), ptr(ws), need, stream()), "wavlm_ctc_loss")
+    return nll, dlogits
+
+
+def ctc_greedy(logits, input_lengths, blank):
+    """wavlm_ctc_greedy on a [B, T, C]-indexed view: (tokens int32 [B, T], counts int32 [B]) on the device"""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    if input_lengths.dtype != torch.int32 or input_lengths.device != dev or input_lengths.numel() != B:
+        raise ValueError("input_lengths: expected an int32 device tensor of B elements")
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.lib().wavlm_ctc_greedy(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(input_lengths.contiguous()), int(blank),
+                                      ptr(tokens), ptr(counts), stream()), "wavlm_ctc_greedy")
+    return tokens, counts
