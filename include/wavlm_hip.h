@@ -189,6 +189,17 @@ int wavlm_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int
 /* y = x + dropout(r, p, seed): residual add of a pre-LN block (unispeech_sat.py:1088-1111 `x = residual + dropout(x)`);
  * same mask as wavlm_dropout for the same seed (the backward of the dropped branch is wavlm_dropout(dy)) */
 int wavlm_dropout_add(const void* x, const void* r, void* y, int64_t n, float p, uint64_t seed, int32_t dtype, void* stream);
+/* UniSpeech's replace-mix (src/fairseq/models/unispeech/unispeech.py:107-112: x.masked_fill(r, 0) + q.masked_fill(~r, 0), then
+ * final_dropout) in one launch: y[row, :] = dropout(sel[row] ? q[row, :] : x[row, :], p, seed).  x, q, y: [rows, D] row-major,
+ * fp32 or bf16, 16-byte aligned, D % 8 == 0; sel: uint8 [rows].  Only the selected source row is read (one read and one write of
+ * rows x D).  The keep decision of element row * D + c is wavlm_dropout's for the same seed and flat index; p = 0 is a plain
+ * select.  _bwd: dx[row, :] = sel[row] ? 0 : dropout(g[row, :]), dq[row, :] = sel[row] ? dropout(g[row, :]) : 0, the mask
+ * recomputed from the seed.  No workspace, no atomics.  -1 for a NULL pointer, D % 8 != 0 or p outside [0, 1); rows == 0 is 0.
+ * Additive to ABI 30 (two new symbols, nothing else changes). */
+int wavlm_replace_mix(const void* x, const void* q, const uint8_t* sel, void* y, int64_t rows, int32_t D, float p, uint64_t seed,
+                      int32_t dtype, void* stream);
+int wavlm_replace_mix_bwd(const void* g, const uint8_t* sel, void* dx, void* dq, int64_t rows, int32_t D, float p, uint64_t seed,
+                          int32_t dtype, void* stream);
 /* out[0] = scale * sum(x^2): features_pen (wavlm.py:486) and the global gradient norm (utils.py:338-388). */
 uint64_t wavlm_sumsq_workspace_bytes(void);
 int wavlm_sumsq(const void* x, int32_t dtype, int64_t n, float scale, float* out, void* workspace, uint64_t ws_bytes,

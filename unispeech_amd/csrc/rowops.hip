@@ -812,6 +812,54 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const T* __restrict__ 
   }
 }
 
+// UniSpeech's replace-mix (models/unispeech/unispeech.py:107-112): y[row] = dropout(sel[row] ? q[row] : x[row]).  Only the
+// selected source row is read: one read and one write of rows x D, the traffic of dropout_kernel, and for the same seed the
+// same keep decision per flat element (keep8 on row * D + c).  d8 = D / 8 chunks per row; th == 0 with sc == 1 (p = 0) is
+// a plain select.  The row of a chunk comes from a 32-bit division whenever the chunk count allows it.
+__device__ __forceinline__ long chunk_row(long i, int d8, bool small) {
+  return small ? (long)((unsigned)i / (unsigned)d8) : i / d8;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void replace_mix_kernel(const T* __restrict__ x, const T* __restrict__ q,
+                                                           const unsigned char* __restrict__ sel, T* __restrict__ y, long n8,
+                                                           int d8, unsigned th, float sc, unsigned long long seed) {
+  const bool small = n8 <= 0xffffffffL, drop = th != 0u || sc != 1.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    float v[8];
+    load8((sel[chunk_row(i, d8, small)] ? q : x) + i * 8, v);
+    if (drop) {
+      const unsigned k = keep8(seed, (unsigned long long)i * 8, th);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = ((k >> e) & 1u) ? v[e] * sc : 0.f;
+    }
+    store8(y + i * 8, v);
+  }
+}
+// its gradient: dropout(g) goes to the selected source, zeros to the other one (mask recomputed from the seed)
+template <typename T>
+__global__ __launch_bounds__(256) void replace_mix_bwd_kernel(const T* __restrict__ g, const unsigned char* __restrict__ sel,
+                                                               T* __restrict__ dx, T* __restrict__ dq, long n8, int d8,
+                                                               unsigned th, float sc, unsigned long long seed) {
+  const bool small = n8 <= 0xffffffffL, drop = th != 0u || sc != 1.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    float v[8], z[8];
+    load8(g + i * 8, v);
+    if (drop) {
+      const unsigned k = keep8(seed, (unsigned long long)i * 8, th);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = ((k >> e) & 1u) ? v[e] * sc : 0.f;
+    }
+    const bool s = sel[chunk_row(i, d8, small)] != 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      z[e] = s ? 0.f : v[e];
+      v[e] = s ? v[e] : 0.f;
+    }
+    store8(dx + i * 8, z);
+    store8(dq + i * 8, v);
+  }
+}
+
 // block partial sums of x^2 (features_pen, global gradient norm) -> part[block] (double).  16-byte loads; eight fp32
 // running sums per thread (each over <= n / (8 * threads) terms) folded into a double per thread, doubles from there on.
 template <typename T>
@@ -1235,6 +1283,46 @@ int wavlm_dropout_add(const void* x, const void* r, void* y, int64_t n, float p,
     WL_LAUNCH((dropout_add_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)r, (bf16_t*)y,
               (long)(n >> 3), th, sc, (unsigned long long)seed);
   else return WL_EINVAL;
+  return wl_check_launch();
+}
+
+// y[row, :] = dropout(sel[row] ? q[row, :] : x[row, :], p, seed): the decision of wavlm_dropout for flat index row * D + c
+int wavlm_replace_mix(const void* x, const void* q, const uint8_t* sel, void* y, int64_t rows, int32_t D, float p, uint64_t seed,
+                      int32_t dtype, void* stream) {
+  if (!x || !q || !sel || !y || rows < 0 || D <= 0 || (D & 7) || p < 0.f || p >= 1.f) return WL_EINVAL;
+  if (dtype != WL_F32 && dtype != WL_BF16) return WL_EINVAL;
+  if (rows == 0) return WL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned th = drop_thresh(p);
+  const float sc = 1.f / (1.f - p);
+  const long n8 = (long)rows * (D >> 3);
+  const unsigned grid = grid_for(n8, 256, 8192);
+  if (dtype == WL_F32)
+    WL_LAUNCH((replace_mix_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)q, sel, (float*)y, n8,
+              (int)(D >> 3), th, sc, (unsigned long long)seed);
+  else
+    WL_LAUNCH((replace_mix_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)q, sel, (bf16_t*)y,
+              n8, (int)(D >> 3), th, sc, (unsigned long long)seed);
+  return wl_check_launch();
+}
+
+// dx[row, :] = sel[row] ? 0 : dropout(g[row, :]), dq[row, :] = sel[row] ? dropout(g[row, :]) : 0
+int wavlm_replace_mix_bwd(const void* g, const uint8_t* sel, void* dx, void* dq, int64_t rows, int32_t D, float p, uint64_t seed,
+                          int32_t dtype, void* stream) {
+  if (!g || !sel || !dx || !dq || rows < 0 || D <= 0 || (D & 7) || p < 0.f || p >= 1.f) return WL_EINVAL;
+  if (dtype != WL_F32 && dtype != WL_BF16) return WL_EINVAL;
+  if (rows == 0) return WL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned th = drop_thresh(p);
+  const float sc = 1.f / (1.f - p);
+  const long n8 = (long)rows * (D >> 3);
+  const unsigned grid = grid_for(n8, 256, 8192);
+  if (dtype == WL_F32)
+    WL_LAUNCH((replace_mix_bwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)g, sel, (float*)dx, (float*)dq, n8,
+              (int)(D >> 3), th, sc, (unsigned long long)seed);
+  else
+    WL_LAUNCH((replace_mix_bwd_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)g, sel, (bf16_t*)dx, (bf16_t*)dq,
+              n8, (int)(D >> 3), th, sc, (unsigned long long)seed);
   return wl_check_launch();
 }
 

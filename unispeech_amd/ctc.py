@@ -10,7 +10,8 @@ is the same wrapper around the other encoder) and the greedy path of src/example
   python -m unispeech_amd.ctc decode CKPT DICT a.wav ...      one greedy transcript per file
 
 Not built, refused by name: the flashlight / KenLM decoder of the criterion (wer_kenlm_model, wer_lexicon, wer_args), reduce=False,
-the seq2seq models of hubert_asr.py / wav2vec2_asr.py, and the UniSpeech multitask model and criterion.
+and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
+a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
 
 Tensors on the host take ctc_reference (loss) and numpy (decode): that path exists for the tests and for tiny inputs.  A device
 tensor always takes the kernels, and a kernel that is missing or refuses its arguments is an error, never a detour.
@@ -470,6 +471,21 @@ def _split_options(options, allow_overrides):
     return opts, over
 
 
+def head_logits(x, proj):
+    """proj(x) through LinearFn for a head whose class count need not be a multiple of 8: the row kernels behind the Linear's
+    backward take widths that are multiples of 8, so zero rows are appended to the head for the call and the logits are the
+    first C columns of its output (a view; wavlm_ctc_loss reads it in place).  Used by _Encoder and unispeech.Unispeech."""
+    from . import functional as F
+    W, b = proj.weight, proj.bias
+    C = W.shape[0]
+    pad = -C % 8
+    if pad:
+        W = torch.cat([W, W.new_zeros(pad, W.shape[1])])
+        b = torch.cat([b, b.new_zeros(pad)])
+    x = F.LinearFn.apply(x, W, b)                                                   # [..., C (+ pad)]
+    return x[..., :C] if pad else x
+
+
 class _Encoder(nn.Module):
     """HubertEncoder (hubert_asr.py:237-340): w2v_model, final_dropout, proj"""
 
@@ -500,16 +516,7 @@ class _Encoder(nn.Module):
                                                   mask=self.apply_mask and self.training)
             x, padding_mask = (res["x"], res["padding_mask"]) if isinstance(res, dict) else res
         x = F.dropout(x, self.final_dropout.p, self.training)
-        W, b = self.proj.weight, self.proj.bias
-        C = W.shape[0]
-        pad = -C % 8
-        if pad:   # the row kernels behind the Linear's backward take widths that are multiples of 8: zero rows are appended to
-            # the head for the call and the logits are the first C columns of its output (a view; the kernel reads it in place)
-            W = torch.cat([W, W.new_zeros(pad, W.shape[1])])
-            b = torch.cat([b, b.new_zeros(pad)])
-        x = F.LinearFn.apply(x, W, b)                                               # [B, T, C (+ pad)], batch-first storage
-        if pad:
-            x = x[..., :C]
+        x = head_logits(x, self.proj)                                               # [B, T, C], batch-first storage
         if tbc:
             x = x.transpose(0, 1)                                                   # T x B x C view: wavlm_ctc_loss reads it in place
         return {"encoder_out": x, "encoder_padding_mask": padding_mask, "padding_mask": padding_mask}
@@ -535,19 +542,29 @@ class EncoderCtc(nn.Module):
     def build(cls, w2v_cfg, num_classes, *, arch="wavlm", task_cfg=None, state_dict=None, **options):
         """HubertEncoder.__init__: the pre-training config with the mask / dropout / layerdrop overrides applied, the model
         built from it, its pre-training weights loaded (strict=False: the heads are gone) and its pre-training modules removed.
-        arch: "wavlm" (WavLMPretrainModel: wavlm, hubert, ils_hubert, unispeech_sat) or "wav2vec2"."""
+        arch: "wavlm" (WavLMPretrainModel: wavlm, hubert, ils_hubert, unispeech_sat), "wav2vec2", or "unispeech": a checkpoint of
+        the multitask model (unispeech.Unispeech) -- the inner Wav2Vec2Model is built from its config, the keys
+        w2v_encoder.w2v_model.* are loaded with the prefix stripped and the pre-training CTC head w2v_encoder.proj.* is dropped
+        (wav2vec2_asr.py:365-366, what the recipe's finetune.sh relies on).  The reference leaves the quantiser modules in
+        place, unused; here they are removed like every other pre-training module."""
         import dataclasses
         opts, over = _split_options(options, allow_overrides=True)
         over["feature_grad_mult"] = opts["feature_grad_mult"]
-        if arch == "wav2vec2":
-            from .wav2vec2 import Wav2Vec2Model
+        if arch in ("wav2vec2", "unispeech"):
+            from .wav2vec2 import Wav2Vec2Config, Wav2Vec2Model
+            if arch == "unispeech":
+                prefix = "w2v_encoder.w2v_model."
+                w2v_cfg = Wav2Vec2Config(**{k: getattr(w2v_cfg, k) for k in Wav2Vec2Config.__dataclass_fields__
+                                            if hasattr(w2v_cfg, k)})
+                if state_dict is not None:
+                    state_dict = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
             over = {k: v for k, v in over.items() if k in type(w2v_cfg).__dataclass_fields__}
             model = Wav2Vec2Model(dataclasses.replace(w2v_cfg, **over))
         elif arch == "wavlm":
             from .pretrain import WavLMPretrainModel
             model = WavLMPretrainModel(dataclasses.replace(w2v_cfg, **over), task_cfg, None)
         else:
-            raise NotImplementedError("arch=%r (wavlm or wav2vec2)" % (arch,))
+            raise NotImplementedError("arch=%r (wavlm, wav2vec2 or unispeech)" % (arch,))
         model.remove_pretraining_modules()      # first: the heads' keys (whatever their shapes) are then simply not loaded
         if state_dict is not None:
             model.load_state_dict(state_dict, strict=False)

@@ -25,13 +25,17 @@ Registered:
              models/wav2vec/wav2vec2_asr.py @register_model("wav2vec_ctc"): one class, the checkpoint at `w2v_path` picks the encoder)
              criterion ctc_mi355x  (ctc.CtcCriterion  <- criterions/ctc.py:65 @register_criterion("ctc"))
              register(override=True) puts them under `hubert_ctc`, `wav2vec_ctc` and `ctc` as well.
+  multitask    unispeech_mi355x  (unispeech.Unispeech  <- models/unispeech/unispeech.py:36 @register_model("unispeech")), criterion
+             unispeech_criterion_mi355x  (unispeech.UnispeechCriterion  <- criterions/unispeech_criterion.py:23); with
+             register(override=True) also `unispeech` / `unispeech_criterion`.  A checkpoint of this model (`_name: unispeech`)
+             at `w2v_path` is fine-tuned through hubert_ctc_mi355x / wav2vec_ctc_mi355x: its inner wav2vec 2.0 weights are loaded.
 Tasks (`hubert_pretraining`, `utterance_mixing_pretraining`) are the reference's own: they are the *caller* of this
 path; the sample dict they collate is consumed unchanged.
 
 fairseq (with omegaconf / hydra) is not installed in the build image; importing this module without it raises
 ImportError and nothing else in unispeech_amd depends on it.
 """
-from dataclasses import dataclass, field, make_dataclass
+from dataclasses import MISSING, dataclass, field, make_dataclass
 from typing import List, Optional
 
 from .pretrain import WavLMCriterion, WavLMPretrainConfig, WavLMPretrainModel
@@ -185,6 +189,62 @@ def _w2v_classes():
     return W2VModel, W2VCriterion, W2VCfg, W2VCritCfg
 
 
+_US_CLASSES = None
+
+
+def _unispeech_classes():
+    """UniSpeech multitask pre-training: Unispeech <- models/unispeech/unispeech.py:36 @register_model("unispeech"),
+    UnispeechCriterion <- criterions/unispeech_criterion.py:23 @register_criterion("unispeech_criterion").  The model's dataclass
+    is the Wav2Vec2MI355XConfig fields plus replace_prob / final_dropout; the criterion's the wav2vec and CTC criterion fields
+    plus mtlalpha.  Built once: the override names and the `*_mi355x` names are the same classes."""
+    global _US_CLASSES
+    if _US_CLASSES is not None:
+        return _US_CLASSES
+    from fairseq.criterions import FairseqCriterion
+    from fairseq.dataclass import FairseqDataclass
+    from fairseq.models import BaseFairseqModel
+    from .unispeech import UniSpeechConfig, Unispeech, UnispeechCriterion
+    fields_ = [(n, f.type, field(default=f.default)) for n, f in UniSpeechConfig.__dataclass_fields__.items()]
+    USCfg = make_dataclass("UniSpeechMI355XConfig", fields_, bases=(FairseqDataclass,))
+    _, _, _, W2VCritCfg = _w2v_classes()
+    _, _, _, CtcCritCfg = _ctc_classes()
+    crit_fields = {}
+    for base in (W2VCritCfg, CtcCritCfg):
+        for n, f in base.__dataclass_fields__.items():
+            if n not in FairseqDataclass.__dataclass_fields__:
+                kw = {"default": f.default} if f.default is not MISSING else {"default_factory": f.default_factory}
+                crit_fields[n] = (n, f.type, field(metadata=dict(f.metadata), **kw))
+    crit_fields["mtlalpha"] = ("mtlalpha", float, field(default=0.5, metadata={"help": "loss weight for multitask learning"}))
+    USCritCfg = make_dataclass("UnispeechCriterionMI355XConfig", list(crit_fields.values()), bases=(FairseqDataclass,))
+
+    class USModel(Unispeech, BaseFairseqModel):
+        def __init__(self, cfg, target_dictionary=None):
+            BaseFairseqModel.__init__(self)
+            Unispeech.__init__(self, cfg, target_dictionary)
+
+        @classmethod
+        def build_model(cls, cfg, task):
+            return cls(cfg, task.target_dictionary)
+
+    class USCrit(UnispeechCriterion, FairseqCriterion):
+        def __init__(self, cfg, task):
+            FairseqCriterion.__init__(self, task)
+            pp = None if cfg.post_process in (None, "none") else cfg.post_process
+            for name in ("wer_kenlm_model", "wer_lexicon", "wer_args"):
+                if getattr(cfg, name, None) is not None:
+                    raise NotImplementedError("%s: the flashlight / KenLM decoder is not built" % name)
+            UnispeechCriterion.__init__(self, task.target_dictionary, cfg.mtlalpha, cfg.infonce, cfg.loss_weights, cfg.log_keys,
+                                        bool(cfg.zero_infinity), bool(cfg.sentence_avg), pp, task=task)
+
+        @staticmethod
+        def reduce_metrics(logging_outputs) -> None:
+            from fairseq import metrics
+            UnispeechCriterion.reduce_metrics(logging_outputs, log_scalar=metrics.log_scalar, log_derived=metrics.log_derived)
+
+    _US_CLASSES = (USModel, USCrit, USCfg, USCritCfg)
+    return _US_CLASSES
+
+
 def _ctc_classes():
     """CTC fine-tuning: EncoderCtc <- hubert_asr.py:138 HubertCtc / wav2vec2_asr.py Wav2VecCtc, CtcCriterion <- criterions/ctc.py:65"""
     from typing import Any
@@ -233,9 +293,12 @@ def _ctc_classes():
             mcfg = dict(scfg["model"]) if "model" in scfg else dict(scfg)
             tnorm = bool(dict(scfg["task"]).get("normalize", False)) if "task" in scfg else bool(mcfg.get("normalize", False))
             assert bool(cfg.normalize) == tnorm, "fine-tuning needs the data normalization of pre-training (--normalize)"
-            arch = "wav2vec2" if mcfg.get("_name", "wavlm") == "wav2vec2" else "wavlm"
+            name = mcfg.get("_name", "wavlm")
+            arch = name if name in ("wav2vec2", "unispeech") else "wavlm"
             if arch == "wav2vec2":
                 from .wav2vec2 import Wav2Vec2Config as Cfg
+            elif arch == "unispeech":   # wav2vec2_asr.py:365-366: the inner model of the multitask checkpoint
+                from .unispeech import UniSpeechConfig as Cfg
             else:
                 Cfg = WavLMPretrainConfig
             wcfg = Cfg(**{k: v for k, v in mcfg.items() if k in Cfg.__dataclass_fields__})
@@ -324,6 +387,16 @@ def register(override: bool = False, fp16_as_bf16=None):
         if "ctc" in CRITERION_REGISTRY:
             CRITERION_REGISTRY["ctc"] = CtcCrit
             CRITERION_DATACLASS_REGISTRY["ctc"] = CtcCritCfg
+        USModel, USCrit, USCfg, USCritCfg = _unispeech_classes()
+        if "unispeech" in MODEL_REGISTRY:
+            MODEL_REGISTRY["unispeech"] = USModel
+            ARCH_MODEL_REGISTRY["unispeech"] = USModel
+            ARCH_MODEL_NAME_REGISTRY["unispeech"] = "unispeech"
+            MODEL_DATACLASS_REGISTRY["unispeech"] = USCfg
+            ARCH_CONFIG_REGISTRY.pop("unispeech", None)
+        if "unispeech_criterion" in CRITERION_REGISTRY:
+            CRITERION_REGISTRY["unispeech_criterion"] = USCrit
+            CRITERION_DATACLASS_REGISTRY["unispeech_criterion"] = USCritCfg
         # the optimizer the Trainer builds in bf16 mode (trainer.py:296-316 `optim.FP16Optimizer.build_optimizer(cfg, params)`)
         # and the data-parallel wrapper it puts around the model (trainer.py:250-261 `models.DistributedFairseqModel(...)`)
         _FusedAdam, FP16Standin, _ = _optim_classes()
@@ -371,6 +444,9 @@ def register(override: bool = False, fp16_as_bf16=None):
         register_model("hubert_ctc_mi355x", dataclass=CtcModelCfg)(CtcModel)
         register_model("wav2vec_ctc_mi355x", dataclass=CtcModelCfg)(type("Wav2VecCtcMI355X", (CtcModel,), {}))
         register_criterion("ctc_mi355x", dataclass=CtcCritCfg)(CtcCrit)
+        USModel, USCrit, USCfg, USCritCfg = _unispeech_classes()
+        register_model("unispeech_mi355x", dataclass=USCfg)(USModel)
+        register_criterion("unispeech_criterion_mi355x", dataclass=USCritCfg)(USCrit)
         from fairseq.optim import register_optimizer
         FusedAdamMI355X, _, AdamCfg = _optim_classes()
         register_optimizer("adam_mi355x", dataclass=AdamCfg)(FusedAdamMI355X)

@@ -1041,6 +1041,29 @@ def dropout(x, p, training=True):
     return DropoutFn.apply(x, p, next_seed())
 
 
+class ReplaceMixFn(torch.autograd.Function):
+    """y[row] = dropout(sel[row] ? q[row] : x[row], p, seed): UniSpeech's replacement of encoder rows by quantised rows followed
+    by final_dropout, one launch each way (csrc/rowops.hip wavlm_replace_mix); nothing but sel is kept for the backward"""
+
+    @staticmethod
+    def forward(ctx, x, q, sel, p, seed):
+        ctx.p, ctx.seed = p, seed
+        ctx.save_for_backward(sel)
+        return ops.replace_mix(x.contiguous(), q.contiguous(), sel, p, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (sel,) = ctx.saved_tensors
+        dx, dq = ops.replace_mix_bwd(dy.contiguous(), sel, ctx.p, ctx.seed)
+        return dx, dq, None, None, None
+
+
+def replace_mix(x, q, sel, p, training=True):
+    """sel uint8 [rows] on the device; the seed comes from next_seed() when dropout is live (p = 0 or eval: a plain select)"""
+    live = training and p > 0
+    return ReplaceMixFn.apply(x, q, sel, float(p) if live else 0.0, next_seed() if live else 0)
+
+
 # -------------------------------------------------------------------------------------------------- loss
 class MaskedPredLossFn(torch.autograd.Function):
     """sum-reduced cross entropy of cos(proj_x, label_embs) / temp against the frame labels, plus the count of

@@ -394,6 +394,41 @@ def dropout_add(x, r, p, seed):
     return y
 
 
+def _replace_mix_args(t, sel):
+    _dev(t); _contig(t); _contig(sel)
+    D = t.shape[-1]
+    rows = t.numel() // D if D else 0
+    if sel.dtype != torch.uint8 or sel.numel() != rows or sel.device != t.device:
+        raise ValueError("sel: expected uint8 [rows = %d] on the tensors' device" % rows)
+    return rows, D
+
+
+def replace_mix(x, q, sel, p, seed):
+    """y[row] = dropout(sel[row] ? q[row] : x[row], p, seed) over the rows of [..., D] tensors (sel uint8, one per row); the keep
+    decisions are those of dropout() for the same seed"""
+    rows, D = _replace_mix_args(x, sel)
+    _contig(q)
+    if q.shape != x.shape or q.dtype != x.dtype or q.device != x.device:
+        raise ValueError("x and q must share shape, dtype and device")
+    y = torch.empty_like(x)
+    if rows == 0:     # (an empty tensor has no address to hand over)
+        return y
+    check(_lib.lib().wavlm_replace_mix(ptr(x), ptr(q), ptr(sel), ptr(y), rows, D, float(p), int(seed), dt(x), stream()),
+          "wavlm_replace_mix")
+    return y
+
+
+def replace_mix_bwd(g, sel, p, seed):
+    """(dx, dq) of replace_mix for the incoming gradient g"""
+    rows, D = _replace_mix_args(g, sel)
+    dx, dq = torch.empty_like(g), torch.empty_like(g)
+    if rows == 0:
+        return dx, dq
+    check(_lib.lib().wavlm_replace_mix_bwd(ptr(g), ptr(sel), ptr(dx), ptr(dq), rows, D, float(p), int(seed), dt(g), stream()),
+          "wavlm_replace_mix_bwd")
+    return dx, dq
+
+
 def sumsq(x, scale=1.0, out=None):
     """scale * sum(x^2) as a 1-element fp32 device tensor (no host sync)"""
     dev = _dev(x); _contig(x)

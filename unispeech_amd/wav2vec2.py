@@ -13,8 +13,16 @@ one-hot x codebook product is a gather, and index lists come from the host-gener
 
 negatives_from_everywhere and codebook_negatives (wav2vec2.py:653-686) are built on the same gathered-row head (the candidate
 table grows by one projected row per frame / per sampled code).  Options of the reference that no shipped recipe uses and
-that raise NotImplementedError: transpose and the non-infonce (BCE)
+that raise NotImplementedError: the non-infonce (BCE)
 criterion (it pairs with wav2vec 1.0's get_targets / get_target_weights, models/wav2vec/wav2vec.py, outside SURVEY.md 8).
+
+UniSpeech's additions to the model (wav2vec2.py:378-381, 652-653, 704-709), used by unispeech_amd.unispeech:
+  transpose=True   final_proj is Linear(final_dim, encoder_embed_dim) and is applied to the candidate table (targets and negatives,
+                   after target_glu) instead of to the encoder rows, which enter the loss unprojected
+  result["q"]      the quantised UNMASKED features of every frame [B, T, .]: final_proj(project_q(.)) with transpose, the raw
+                   codebook rows without.  The reference computes it in every forward; here it is computed when someone reads it
+                   (transpose, or return_q = True, which Unispeech sets): a plain wav2vec 2.0 step keeps its launches
+  mask=False       with features_only=False (the reference's validation path, x[None].view(B, -1, C)): every frame is a position
 """
 import ast
 import math
@@ -167,8 +175,10 @@ class GumbelVectorQuantizer(nn.Module):
 class Wav2Vec2Model(nn.Module):
     def __init__(self, cfg: Wav2Vec2Config):
         super().__init__()
-        if getattr(cfg, "transpose", False):
-            raise NotImplementedError("wav2vec 2.0 option transpose is not supported by the HIP path")
+        self.transpose = bool(getattr(cfg, "transpose", False))
+        if self.transpose and not cfg.quantize_targets:
+            raise ValueError("transpose needs quantize_targets (the reference reads results['q'], which only the quantiser sets)")
+        self.return_q = False   # True: result["q"] without transpose as well (the raw codebook rows, wav2vec2.py:653)
         self.negatives_from_everywhere = bool(getattr(cfg, "negatives_from_everywhere", False))
         self.codebook_negatives = int(getattr(cfg, "codebook_negatives", 0))
         if self.codebook_negatives > 0 and not cfg.quantize_targets:
@@ -223,7 +233,8 @@ class Wav2Vec2Model(nn.Module):
         self.target_glu = None
         if cfg.target_glu:  # wav2vec2.py:371-375
             self.target_glu = nn.Sequential(nn.Linear(final_dim, final_dim * 2), nn.GLU())
-        self.final_proj = nn.Linear(cfg.encoder_embed_dim, final_dim)
+        self.final_proj = (nn.Linear(final_dim, cfg.encoder_embed_dim) if self.transpose   # wav2vec2.py:378-381
+                           else nn.Linear(cfg.encoder_embed_dim, final_dim))
 
     @classmethod
     def build_model(cls, cfg, task=None):
@@ -317,24 +328,29 @@ class Wav2Vec2Model(nn.Module):
                                            prezeroed=True)
         if features_only:
             return {"x": x, "padding_mask": padding_mask, "features": unmasked, "layer_results": layer_results}
-        if mask_np is None:
-            raise NotImplementedError("the pre-training forward needs a time mask (mask=True, mask_prob > 0)")
 
         # -- targets y = (quantised) unmasked features at the masked frames (wav2vec2.py:617-664)
-        idx_np = np.flatnonzero(mask_np.reshape(-1)).astype(np.int32)
-        S = int(idx_np.size)
-        Tm = S // B
-        assert Tm * B == S, "rows must hold equal numbers of masked frames (compute_mask_indices guarantees it)"
-        inv_np = np.full(B * T, -1, dtype=np.int32)
-        inv_np[idx_np] = np.arange(S, dtype=np.int32)
-        idx, inv = F.h2d(idx_np, dev), F.h2d(inv_np, dev)
-        y = F.GatherRowsFn.apply(unmasked.reshape(B * T, -1), idx, inv)                # [S, C], row = b * Tm + t
+        every = mask_np is None   # no time mask (mask=False: validation of UniSpeech): mask_indices is None in the reference and
+        if every:                 # x[None].view(B, -1, C), y = unmasked_features make every frame a position: the identity gather
+            idx_np = np.arange(B * T, dtype=np.int32)
+            S, Tm = B * T, T
+            y = unmasked.reshape(B * T, -1)
+        else:
+            idx_np = np.flatnonzero(mask_np.reshape(-1)).astype(np.int32)
+            S = int(idx_np.size)
+            Tm = S // B
+            assert Tm * B == S, "rows must hold equal numbers of masked frames (compute_mask_indices guarantees it)"
+            inv_np = np.full(B * T, -1, dtype=np.int32)
+            inv_np[idx_np] = np.arange(S, dtype=np.int32)
+            idx, inv = F.h2d(idx_np, dev), F.h2d(inv_np, dev)
+            y = F.GatherRowsFn.apply(unmasked.reshape(B * T, -1), idx, inv)            # [S, C], row = b * Tm + t
         result = {"features": x, "feature_padding_mask": padding_mask}
         if inq is not None:  # overwritten by the target quantiser's values below, as in the reference
             result.update(prob_perplexity=inq["prob_perplexity"], code_perplexity=inq["code_perplexity"],
                           num_vars=inq["num_vars"], temp=inq["temp"])
         nfe, cbn = self.negatives_from_everywhere, self.codebook_negatives
         cand = None  # candidates of negatives_from_everywhere: one projected row per frame [B * T, F]
+        need_q, q_res = self.transpose or self.return_q, None
         if self.quantizer is not None:
             q = self.quantizer(y.view(B, Tm, -1))
             y = q["x"].reshape(S, -1)
@@ -343,6 +359,14 @@ class Wav2Vec2Model(nn.Module):
             if nfe:  # the reference's second quantiser pass over ALL frames supplies the candidates (wav2vec2.py:653-661)
                 q_all = self.quantizer(unmasked.reshape(B, T, -1))["x"].reshape(B * T, -1)
                 cand = F.LinearFn.apply(q_all, self.project_q.weight, self.project_q.bias)
+                if need_q and not self.transpose:
+                    q_res = q_all.view(B, T, -1)
+            elif need_q:  # the second pass is read: run it where the reference does (same place in the host-noise stream)
+                q_all = self.quantizer(unmasked.reshape(B, T, -1))["x"].reshape(B * T, -1)
+                q_res = q_all.view(B, T, -1)
+                if self.transpose:
+                    q_res = F.LinearFn.apply(F.LinearFn.apply(q_all, self.project_q.weight, self.project_q.bias),
+                                             self.final_proj.weight, self.final_proj.bias).view(B, T, -1)
             else:
                 self.quantizer.burn_host_noise(B * T)
             y = F.LinearFn.apply(y, self.project_q.weight, self.project_q.bias)          # [S, F]
@@ -367,12 +391,23 @@ class Wav2Vec2Model(nn.Module):
             cb = F.LinearFn.apply(codes.to(table.dtype), self.project_q.weight, self.project_q.bias)
             cols.append(table.shape[0] + torch.arange(cbn).view(1, cbn) * S + torch.arange(S).view(S, 1))
             table = torch.cat([table, cb], dim=0)
-        xs = F.GatherRowsFn.apply(x.reshape(B * T, -1), idx, inv)
-        xs = F.LinearFn.apply(xs, self.final_proj.weight, self.final_proj.bias)      # [S, F]
+        xs = x.reshape(B * T, -1) if every else F.GatherRowsFn.apply(x.reshape(B * T, -1), idx, inv)
+        if not self.transpose:
+            xs = F.LinearFn.apply(xs, self.final_proj.weight, self.final_proj.bias)  # [S, F]
         idx_full = F.h2d(torch.cat(cols, dim=1).to(torch.int32), dev)
         if self.target_glu is not None:  # y and the negatives alike (wav2vec2.py:697-699): per row of the candidate table
             tg = self.target_glu[0]
+            if self.transpose and cand is not None:   # results["q"] skips the GLU (wav2vec2.py:707): its own final_proj
+                q_res = F.LinearFn.apply(cand, self.final_proj.weight, self.final_proj.bias).view(B, T, -1)
             table = F.GLUFn.apply(F.LinearFn.apply(table.contiguous(), tg.weight, tg.bias))
+        if self.transpose:  # wav2vec2.py:704-707: final_proj on targets and negatives, i.e. per row of the candidate table; the
+            # encoder rows xs stay [S, D].  With negatives_from_everywhere rows S .. S + B T of the table ARE
+            # final_proj(project_q(quantised frame)): results["q"] is a view of them, no second GEMM
+            table = F.LinearFn.apply(table.contiguous(), self.final_proj.weight, self.final_proj.bias)
+            if cand is not None and q_res is None:
+                q_res = table[S:S + B * T].view(B, T, -1)
+        if q_res is not None:
+            result["q"] = q_res
         y = table
         loss, ncorrect = F.SampledNegativesLossFn.apply(xs, y, idx_full, self.logit_temp)
         result["head"] = {"loss": loss, "correct": ncorrect, "count": S, "x": xs, "y": y, "idx": idx_full, "B": B, "Tm": Tm}
