@@ -759,6 +759,33 @@ int wavlm_ctc_greedy(const void* logits, int32_t dtype, int64_t stride_b, int64_
                      const int32_t* input_lengths, int32_t blank, int32_t* tokens, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC validation scoring (csrc/ctc_score.hip; additive to ABI 30: three new symbols, nothing else changes): the greedy decode of
+ * wavlm_ctc_greedy and, in the same launch, the error counts of src/fairseq/criterions/ctc.py:161-226 -- unit and word edit
+ * distances of every sample's decode against its target -- so that only [B, 4] integers have to leave the device.
+ *   logits, dtype, strides, input_lengths, blank, tokens, counts   exactly as wavlm_ctc_greedy takes and writes them
+ *   targets  int32 [B, Lt] row-major, padded (the criterion's sample["target"]); pad and eos are dropped wherever they stand
+ *   cls      uint8 [C]: 0 = DROP (the dictionary's string() omits the token), 1 = SEP (the word boundary `|`), 2 = LETTER.  A
+ *            target id outside [0, C) never indexes the table: it is a LETTER, compared by value
+ *   each_token_a_word  0: DROP tokens are removed, then words are the maximal runs of LETTER tokens between SEPs (post_process =
+ *            "letter": a dropped token inside a word does not split it; leading, trailing and repeated separators make no empty
+ *            words).  1: every non-DROP token is a word of its own (post_process = None)
+ *   out      int32 [B, 4]: c_err = Levenshtein(decode, target units), c_len = target units, w_err = Levenshtein(decode's words,
+ *            target's words), w_len = target's words.  The decode keeps whatever pad / eos / unk the argmax produced.  Two words
+ *            are equal when their token ids are (a hash only spares the comparison): all integer, exact
+ *   workspace  wavlm_ctc_score_workspace_bytes(B, T, Lt) bytes, 4-byte aligned: per sample the target's units, both word streams
+ *            and their span tables (first token, length, hash): 5 Lt + 4 T ints
+ * One launch, one workgroup per sample; the two DPs run one wave each with the row in registers (no atomics, nothing that
+ * depends on B or on the sample's place in the batch).  wavlm_ctc_score_supported (host): 1 for T >= 1 and 0 <= Lt <= 1024 (64
+ * lanes x 16 columns); wavlm_ctc_score returns -1 otherwise, and for a NULL pointer, a bad view or a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_ctc_score_supported(int32_t T, int32_t Lt);
+uint64_t wavlm_ctc_score_workspace_bytes(int32_t B, int32_t T, int32_t Lt);
+int wavlm_ctc_score(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                    const int32_t* input_lengths, int32_t blank, const int32_t* targets, int32_t Lt, int32_t pad, int32_t eos,
+                    const uint8_t* cls, int32_t each_token_a_word, int32_t* tokens, int32_t* counts, int32_t* out,
+                    void* workspace, uint64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

@@ -221,6 +221,10 @@ SIGNATURES = {
     "wavlm_ctc_loss": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp,
                                c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_ctc_greedy": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "wavlm_ctc_score_supported": (c_i32, [c_i32, c_i32]),
+    "wavlm_ctc_score_workspace_bytes": (c_u64, [c_i32, c_i32, c_i32]),
+    "wavlm_ctc_score": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                c_vp, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

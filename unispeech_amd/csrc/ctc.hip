@@ -30,11 +30,9 @@
 // occurrences are walked in ascending s; the blank's up to L + 1 positions are summed by one wave, each lane its own positions
 // in ascending s, then one xor butterfly.  Nothing depends on B, on the sample's place in the batch or on the other samples:
 // results are bitwise reproducible and a sample's loss and gradient are the same bits alone and in any batch.
-#include "common.hpp"
-#include <math.h>
+#include "ctc_decode.hpp"
 #include "../../include/wavlm_hip.h"
 
-#define CT_NT 256
 #define CT_MAXL 1023                 // labels per sample
 #define CT_SP 2048                   // extended positions, padded (2 * CT_MAXL + 1 = 2047)
 #define CT_MAXC 1024                 // classes
@@ -95,11 +93,6 @@ template <int DT> __device__ __forceinline__ float ct_ld(const void* p, long i) 
 }
 template <int DT> __device__ __forceinline__ void ct_st(void* p, long i, float v) {
   if (DT == WL_F32) ((float*)p)[i] = v; else ((bf16_t*)p)[i] = f2bf(v);
-}
-
-__device__ __forceinline__ int ct_len(const int* __restrict__ in_len, int b, int T) {
-  const int v = in_len[b];
-  return v < 0 ? 0 : (v > T ? T : v);
 }
 
 // ---- (a) lse[b, t] = log sum_c exp x[b, t, c], rows at or beyond the input length are skipped (never read) ----
@@ -339,50 +332,12 @@ __global__ __launch_bounds__(CT_NT) void ctc_beta_grad_kernel(const void* __rest
   }
 }
 
-// ---- greedy decode: argmax per frame (ties to the lowest class), repeats collapsed, blanks dropped ----
+// ---- greedy decode: argmax per frame (ties to the lowest class), repeats collapsed, blanks dropped (ctc_decode.hpp) ----
 __global__ __launch_bounds__(CT_NT) void ctc_greedy_kernel(const void* __restrict__ x, int dt, long sb, long st, int T, int C,
     const int* __restrict__ in_len, int blank, int* __restrict__ tokens, int* __restrict__ counts) {
   __shared__ int s_arg[CT_NT];
-  __shared__ int s_base, s_last;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-  const int Tb = ct_len(in_len, b, T);
-  const long xb = (long)b * sb;
-  int* tok = tokens + (long)b * T;
-  if (tid == 0) { s_base = 0; s_last = -1; }
-  __syncthreads();
-  for (int t0 = 0; t0 < Tb; t0 += CT_NT) {   // a chunk of CT_NT frames: a wave takes a frame at a time
-    const int n = Tb - t0 < CT_NT ? Tb - t0 : CT_NT;
-    for (int f = wave; f < n; f += CT_NT / 64) {
-      const long xt = xb + (long)(t0 + f) * st;
-      float best = -INFINITY;
-      int arg = -1;                          // a lane without a class (C < 64) stays at -1
-      for (int c = lane; c < C; c += 64) {   // ascending c per lane: the first maximum stays
-        const float v = ld_elem(x, xt + c, dt);
-        if (arg < 0 || v > best) { best = v; arg = c; }
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oa = __shfl_xor(arg, o, 64);
-        if (oa >= 0 && (arg < 0 || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-      }
-      if (lane == 0) s_arg[f] = arg;
-    }
-    __syncthreads();
-    if (tid == 0) {   // the collapse is sequential in t: at most CT_NT steps per chunk on one lane
-      int last = s_last, base = s_base;
-      for (int f = 0; f < n; ++f) {
-        const int a = s_arg[f];
-        if (a != last && a != blank) tok[base++] = a;
-        last = a;
-      }
-      s_last = last; s_base = base;
-    }
-    __syncthreads();
-  }
-  const int cnt = s_base;
-  for (int t = cnt + tid; t < T; t += CT_NT) tok[t] = -1;
-  if (tid == 0) counts[b] = cnt;
+  __shared__ int s_state[2];
+  ct_greedy_sample(x, dt, sb, st, T, C, in_len, blank, tokens, counts, blockIdx.x, s_arg, s_state);
 }
 
 template <int PER, int DT>
@@ -393,16 +348,6 @@ static void ct_launch(int B, hipStream_t s, const void* x, long sb, long st, int
             Lmax, lse, alpha, nll64);
   WL_LAUNCH((ctc_beta_grad_kernel<PER, DT>), dim3((unsigned)B), dim3(CT_NT), 0, s, x, sb, st, T, C, targets, toff, ntgt, in_len,
             blank, Lmax, lse, (const float*)alpha, (const double*)nll64, grad_out, zero_infinity, nll, dx);
-}
-
-// the B x T x C view with unit class stride must not overlap itself: rows apart by at least C along one axis, samples (or frames)
-// apart by at least the other axis's whole extent
-static inline int ct_view_ok(int64_t B, int64_t T, int64_t C, int64_t sb, int64_t st) {
-  if (sb < 0 || st < 0) return 0;
-  if (B > 1 && T > 1) return (st >= C && sb >= T * st) || (sb >= C && st >= B * sb);
-  if (T > 1) return st >= C;
-  if (B > 1) return sb >= C;
-  return 1;
 }
 
 extern "C" {

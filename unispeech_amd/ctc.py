@@ -7,18 +7,23 @@ is the same wrapper around the other encoder) and the greedy path of src/example
   greedy_decode   argmax / collapse repeats / drop blanks on the device (wavlm_ctc_greedy)
   CtcCriterion    criterions/ctc.py: sum-reduced loss, ntokens / nsentences / sample_size, error counts in eval
   EncoderCtc      hubert_asr.py:138-178, 237-340 around any pre-training model of this package
+  error_counts    the validation counts (unit / word edit distances) of a batch: wavlm_ctc_score (csrc/ctc_score.hip), one launch
   python -m unispeech_amd.ctc decode CKPT DICT a.wav ...      one greedy transcript per file
+  python -m unispeech_amd.ctc score CKPT DICT MANIFEST.tsv LABELS.ltr      UER / WER over a manifest
 
 Not built, refused by name: the flashlight / KenLM decoder of the criterion (wer_kenlm_model, wer_lexicon, wer_args), reduce=False,
 and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
 a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
 
 Tensors on the host take ctc_reference (loss) and numpy (decode): that path exists for the tests and for tiny inputs.  A device
-tensor always takes the kernels, and a kernel that is missing or refuses its arguments is an error, never a detour.
+tensor always takes the kernels, and a kernel that is missing or refuses its arguments is an error, never a detour.  The one
+stated exception is error_counts: where word_classes() finds that token spans would not compare as the dictionary's strings do,
+or the targets are wider than wavlm_ctc_score_supported allows, the counts come from the host loop -- the same integers.
 """
 import argparse
 import contextlib
 import math
+import os
 import sys
 
 import numpy as np
@@ -298,6 +303,14 @@ class LetterDictionary:
     def string(self, tokens):
         return " ".join(self.symbols[int(t)] for t in tokens if int(t) not in (0, 1, 2))
 
+    def index(self, symbol):
+        """the symbol's id, <unk> for one the dictionary does not have (fairseq's Dictionary.index)"""
+        n, ids = self.__dict__.get("_ids", (0, None))
+        if n != len(self.symbols):                     # the first of equal symbols, as the file's order has it
+            ids = {sym: i for i, sym in reversed(list(enumerate(self.symbols)))}
+            self._ids = (len(self.symbols), ids)
+        return ids.get(symbol, self.unk())
+
 
 class _IndexDictionary:
     """stands in when the criterion is given three integers: a token's string is its index"""
@@ -316,6 +329,138 @@ class _IndexDictionary:
 
     def string(self, tokens):
         return " ".join(str(int(t)) for t in tokens)
+
+
+# --------------------------------------------------------------------------------------------------------- error counts
+DROP, SEP, LETTER = 0, 1, 2            # the classes of wavlm_ctc_score's table (include/wavlm_hip.h)
+_UNSET = object()
+
+
+def _known_dictionary(d):
+    t = type(d)
+    return t in (LetterDictionary, _IndexDictionary) or (t.__name__ == "Dictionary" and t.__module__.startswith("fairseq."))
+
+
+def word_classes(dictionary, C, post_process="letter"):
+    """The uint8 table [C] from which wavlm_ctc_score builds its words -- DROP: dictionary.string() omits the token, SEP: the word
+    boundary `|` (under "letter"), LETTER: anything else -- or None when comparing token spans on the device would not be
+    exactly what post_process(dictionary.string(...)).split() compares on the host:
+      * the dictionary is not a LetterDictionary, an _IndexDictionary or fairseq's Dictionary, or probing it raises;
+      * a LETTER's string contains whitespace (or, under "letter", a `|`);
+      * two LETTERs share a string; or, under "letter", one LETTER's string is a prefix of another's (words are concatenations
+        there: "<" next to "<unk>", or the indices "1" and "12" of an _IndexDictionary, make two token spans one string).
+    A dictionary longer than C is probed to its end: a target may name those symbols, and the kernel takes an id beyond C as a
+    LETTER compared by value, so they must be LETTERs under the same rules."""
+    letter = post_process == "letter"
+    if not letter and post_process not in (None, "none"):
+        return None
+    if not _known_dictionary(dictionary):
+        return None
+    C = int(C)
+    try:
+        n = max(C, len(dictionary))
+    except TypeError:
+        n = C
+    tab = np.empty(C, dtype=np.uint8)
+    letters = []
+    try:
+        for i in range(n):
+            s = dictionary.string([i])
+            if not isinstance(s, str):
+                return None
+            if s == "":
+                k = DROP
+            elif letter and s == "|":
+                k = SEP
+            else:
+                if any(ch.isspace() for ch in s) or (letter and "|" in s):
+                    return None
+                k = LETTER
+                letters.append(s)
+            if i < C:
+                tab[i] = k
+            elif k != LETTER:
+                return None
+    except Exception:
+        return None
+    letters.sort()
+    for a, b in zip(letters, letters[1:]):
+        if a == b or (letter and b.startswith(a)):
+            return None
+    return tab
+
+
+def _host_counts(logits, input_lengths, targets, dictionary, symbol, blank):
+    """the loop of criterions/ctc.py:200-226 on the host: per sample (c_err, c_len, w_err, w_len), and the decodes"""
+    T, B = logits.shape[0], logits.shape[1]
+    il = None if input_lengths is None else _host_ints(input_lengths, "input_lengths")
+    with torch.no_grad():
+        decoded = greedy_decode(logits, il, blank)
+    labels = torch.as_tensor(targets).detach().cpu()
+    pad, eos = dictionary.pad(), dictionary.eos()
+    out = np.zeros((B, 4), dtype=np.int64)
+    for b, (pred, t) in enumerate(zip(decoded, labels)):
+        targ = t[(t != pad) & (t != eos)].tolist()
+        targ_words = post_process(dictionary.string(targ), symbol).split()
+        pred_words = post_process(dictionary.string(pred), symbol).split()
+        out[b] = (edit_distance(pred, targ), len(targ), edit_distance(pred_words, targ_words), len(targ_words))
+    return out, decoded
+
+
+def sample_error_counts(logits, input_lengths, targets, dictionary, post_process="letter", blank=None, *, classes=_UNSET,
+                        hypotheses=True):
+    """Per sample what error_counts sums: (int64 numpy [B, 4] = c_err, c_len, w_err, w_len; the B greedy decodes as token lists, or
+    None with hypotheses=False on the device path, which then copies nothing but the [B, 4] counts to the host).
+    logits [T, B, C]; input_lengths [B] or None; targets [B, Lt] padded with the dictionary's pad() / eos().
+    classes: word_classes(dictionary, C, post_process) if the caller has it already (as a numpy array or a device tensor)."""
+    symbol = None if post_process in (None, "none") else post_process
+    _post_process("", symbol)
+    if blank is None:
+        blank = dictionary.bos()
+    T, B, C = logits.shape
+    targets = torch.as_tensor(targets)
+    if targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("targets: expected [B, Lt] with B = %d rows" % B)
+    device = torch.is_tensor(logits) and logits.is_cuda and os.environ.get("WAVLM_CTC_SCORE_HOST", "") != "1"
+    if device:
+        from . import ops
+        device = ops.ctc_score_supported(T, targets.shape[1])
+    if device:
+        if classes is _UNSET:
+            classes = word_classes(dictionary, C, symbol)
+        device = classes is not None
+    if not device:
+        return _host_counts(logits, input_lengths, targets, dictionary, symbol, blank)
+    dev = logits.device
+    x = logits.detach().transpose(0, 1)
+    if x.shape[2] > 1 and x.stride(2) != 1:
+        x = x.contiguous()
+    if input_lengths is None:
+        il = torch.full((B,), T, dtype=torch.int32, device=dev)
+    else:
+        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    cls = torch.as_tensor(classes).to(device=dev, dtype=torch.uint8).contiguous()
+    t = targets.detach().to(device=dev, dtype=torch.int32).contiguous()
+    counts, tokens, token_counts = ops.ctc_score(x, il, t, dictionary.pad(), dictionary.eos(), blank, cls, symbol is None)
+    decoded = None
+    if hypotheses:
+        tok, cnt = tokens.cpu().numpy(), token_counts.cpu().numpy()
+        decoded = [[int(v) for v in tok[b, :cnt[b]]] for b in range(B)]
+    return counts.cpu().numpy().astype(np.int64), decoded
+
+
+def error_counts(logits, input_lengths, targets, dictionary, post_process="letter", blank=None, *, classes=_UNSET):
+    """The validation counts of criterions/ctc.py:161-226 for one batch: {c_errors, c_total, w_errors, wv_errors, w_total} (unit
+    and word edit distances of the greedy decode against the targets and their lengths; wv_errors = w_errors: the KenLM decoder
+    is not built).  logits [T, B, C], input_lengths [B] or None, targets [B, Lt] padded; blank defaults to dictionary.bos().
+
+    Device logits take wavlm_ctc_score -- decode, both distances and both lengths in one launch, [B, 4] integers copied back --
+    when word_classes() has a table for this dictionary and wavlm_ctc_score_supported(T, Lt) says yes; otherwise, for host
+    logits, and under WAVLM_CTC_SCORE_HOST=1, the host loop (greedy_decode + edit_distance per sample).  Both give the same
+    integers (target ids are non-negative)."""
+    n, _ = sample_error_counts(logits, input_lengths, targets, dictionary, post_process, blank, classes=classes, hypotheses=False)
+    c_err, c_len, w_err, w_len = (int(v) for v in n.sum(0))
+    return {"wv_errors": w_err, "w_errors": w_err, "w_total": w_len, "c_errors": c_err, "c_total": c_len}
 
 
 # ------------------------------------------------------------------------------------------------------------ criterion
@@ -379,21 +524,19 @@ class CtcCriterion(nn.Module):
         logging_output = {"loss": float(loss.detach()), "ntokens": ntokens, "nsentences": sample["id"].numel(),
                           "sample_size": sample_size}
         if not model.training:
-            il = _host_ints(input_lengths, "input_lengths")
-            with torch.no_grad():
-                decoded = greedy_decode(logits, il, self.blank_idx)
-            labels = (sample["target_label"] if "target_label" in sample else target).detach().cpu()
-            c_err = c_len = w_errs = w_len = 0
-            for pred, t in zip(decoded, labels):
-                targ = t[(t != self.pad_idx) & (t != self.eos_idx)].tolist()
-                c_err += edit_distance(pred, targ)
-                c_len += len(targ)
-                targ_words = post_process(self.dictionary.string(targ), self.post_process).split()
-                pred_words = post_process(self.dictionary.string(pred), self.post_process).split()
-                w_errs += edit_distance(pred_words, targ_words)
-                w_len += len(targ_words)
-            logging_output.update(wv_errors=w_errs, w_errors=w_errs, w_total=w_len, c_errors=c_err, c_total=c_len)
+            labels = sample["target_label"] if "target_label" in sample else target
+            logging_output.update(error_counts(logits, input_lengths, labels, self.dictionary, self.post_process, self.blank_idx,
+                                               classes=self._classes(logits.shape[2], logits.device) if logits.is_cuda else None))
         return loss, sample_size, logging_output
+
+    def _classes(self, C, device):
+        """word_classes of this criterion's dictionary for C classes, on `device`: built once (C probes of dictionary.string)"""
+        cache = self.__dict__.setdefault("_cls_cache", {})
+        key = (int(C), str(device))
+        if key not in cache:
+            tab = word_classes(self.dictionary, C, self.post_process)
+            cache[key] = None if tab is None else torch.from_numpy(tab).to(device)
+        return cache[key]
 
     @staticmethod
     def reduce_metrics(logging_outputs, log_scalar=None, log_derived=None):
@@ -620,11 +763,124 @@ def parse_args(argv=None):
     d.add_argument("wavs", nargs="+")
     d.add_argument("--post-process", default="letter", choices=["letter", "none"])
     d.add_argument("--bf16", action="store_true")
+    c = sub.add_parser("score", help="UER / WER of the greedy decode over a manifest (error_counts per batch)")
+    c.add_argument("ckpt")
+    c.add_argument("dict")
+    c.add_argument("manifest", help="fairseq manifest: the root directory, then `relpath<TAB>nsamples` per line")
+    c.add_argument("labels", help="one line of space-separated symbols per utterance (.ltr)")
+    c.add_argument("--batch-seconds", type=float, default=160.0, help="padded audio per batch, in seconds")
+    c.add_argument("--post-process", default="letter", choices=["letter", "none"])
+    c.add_argument("--bf16", action="store_true")
+    c.add_argument("--results", default=None, metavar="DIR", help="write hypo.units, hypo.word, ref.units, ref.word there")
     return p.parse_args(argv)
+
+
+def read_manifest(path):
+    """[(path of the audio file, its number of samples)] of a fairseq manifest"""
+    with open(path, encoding="utf-8") as f:
+        lines = f.read().splitlines()
+    if not lines:
+        raise ValueError("%s: empty manifest (line 1 is the root directory)" % path)
+    root, out = lines[0].strip(), []
+    for no, line in enumerate(lines[1:], 2):
+        if not line.strip():
+            continue
+        parts = line.split("\t")
+        if len(parts) < 2 or not parts[1].strip().isdigit():
+            raise ValueError("%s:%d: expected `relpath<TAB>nsamples`" % (path, no))
+        out.append((os.path.join(root, parts[0]), int(parts[1])))
+    return out
+
+
+def read_labels(path, dictionary, n_utterances=None):
+    """one list of token ids per line of a label file (space-separated symbols, no eos appended: the fine-tuning task's
+    LabelEncoder); a line count other than the manifest's is refused"""
+    with open(path, encoding="utf-8") as f:
+        lines = f.read().splitlines()
+    if n_utterances is not None and len(lines) != n_utterances:
+        raise ValueError("%s: %d label lines, but the manifest lists %d utterances" % (path, len(lines), n_utterances))
+    return [[dictionary.index(sym) for sym in line.split()] for line in lines]
+
+
+def length_batches(sizes, max_samples):
+    """indices of the utterances, sorted by length (ties by index) and cut where the batch's padded size -- its longest
+    utterance times its count -- would pass max_samples; an utterance longer than that is a batch of its own"""
+    order = sorted(range(len(sizes)), key=lambda i: (sizes[i], i))
+    out, cur = [], []
+    for i in order:                                   # ascending: the newcomer is the batch's longest
+        if cur and sizes[i] * (len(cur) + 1) > max_samples:
+            out.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        out.append(cur)
+    return out
+
+
+def score(a):
+    """`score`: the scoring half of examples/speech_recognition/infer.py and compute_WER.py with the greedy decode"""
+    from .kmeans import read_wav
+    d = LetterDictionary.load(a.dict)
+    symbol = None if a.post_process == "none" else "letter"
+    entries = read_manifest(a.manifest)
+    labels = read_labels(a.labels, d, len(entries))
+    model, normalize = load_ctc_checkpoint(a.ckpt, len(d))
+    if a.bf16:
+        model = model.to(torch.bfloat16)
+    dtype = next(model.parameters()).dtype
+    classes = word_classes(d, len(d), symbol)
+    total = np.zeros(4, dtype=np.int64)
+    hyps = [None] * len(entries)
+    for batch in length_batches([n for _, n in entries], int(a.batch_seconds * 16000)):
+        wavs = []
+        for i in batch:
+            wav, sr = read_wav(entries[i][0])
+            if sr != 16000:
+                raise NotImplementedError("%s: %d Hz; the models take 16 kHz audio (unispeech_amd.resample converts)"
+                                          % (entries[i][0], sr))
+            x = torch.as_tensor(wav, dtype=torch.float32)
+            wavs.append(torch.nn.functional.layer_norm(x, x.shape) if normalize else x)
+        n = max(w.numel() for w in wavs)
+        src = torch.zeros(len(batch), n)
+        pm = torch.ones(len(batch), n, dtype=torch.bool)
+        for r, w in enumerate(wavs):
+            src[r, :w.numel()] = w
+            pm[r, :w.numel()] = False
+        Lt = max(1, max(len(labels[i]) for i in batch))
+        target = torch.full((len(batch), Lt), d.pad(), dtype=torch.long)
+        for r, i in enumerate(batch):
+            target[r, :len(labels[i])] = torch.tensor(labels[i], dtype=torch.long)
+        with torch.no_grad():
+            out = model(source=src.cuda().to(dtype), padding_mask=pm.cuda() if bool(pm.any()) else None)
+        logits = out["encoder_out"]
+        il = None if out["padding_mask"] is None else (~out["padding_mask"]).sum(-1)
+        counts, decoded = sample_error_counts(logits, il, target, d, symbol, d.bos(), classes=classes,
+                                              hypotheses=a.results is not None)
+        total += counts.sum(0)
+        if decoded is not None:
+            for i, toks in zip(batch, decoded):
+                hyps[i] = toks
+    c_err, c_len, w_err, w_len = (int(v) for v in total)
+    print("UER %.3f%% WER %.3f%% c_errors %d c_total %d w_errors %d w_total %d"
+          % (c_err * 100.0 / max(c_len, 1), w_err * 100.0 / max(w_len, 1), c_err, c_len, w_err, w_len))
+    if a.results is not None:
+        os.makedirs(a.results, exist_ok=True)
+        files = {"hypo.units": [], "hypo.word": [], "ref.units": [], "ref.word": []}
+        for i, (hyp, ref) in enumerate(zip(hyps, labels)):          # infer.py:120-148, speaker None, id = the utterance's index
+            for kind, toks in (("hypo", hyp), ("ref", ref)):
+                units = d.string(toks)
+                files[kind + ".units"].append("%s (None-%d)" % (units, i))
+                files[kind + ".word"].append("%s (None-%d)" % (post_process(units, symbol), i))
+        for name, lines in files.items():
+            with open(os.path.join(a.results, name), "w", encoding="utf-8") as f:
+                f.write("".join(line + "\n" for line in lines))
+    return 0
 
 
 def main(argv=None):
     a = parse_args(argv)
+    if a.cmd == "score":
+        return score(a)
     from .kmeans import read_wav
     d = LetterDictionary.load(a.dict)
     model, normalize = load_ctc_checkpoint(a.ckpt, len(d))

@@ -1034,3 +1034,39 @@ def ctc_greedy(logits, input_lengths, blank):
     check(_lib.lib().wavlm_ctc_greedy(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(input_lengths.contiguous()), int(blank),
                                       ptr(tokens), ptr(counts), stream()), "wavlm_ctc_greedy")
     return tokens, counts
+
+
+def ctc_score_supported(T, Lt):
+    return bool(_lib.lib().wavlm_ctc_score_supported(int(T), int(Lt)))
+
+
+def ctc_score(logits, input_lengths, targets, pad, eos, blank, cls, each_token_a_word=False):
+    """wavlm_ctc_score on a [B, T, C]-indexed view (the rules of ctc_greedy): the greedy decode and the error counts of every sample
+    in one launch.  targets int32 [B, Lt] padded, cls uint8 [C] (0 DROP, 1 SEP, 2 LETTER), both on the device.  Returns
+    (counts int32 [B, 4] = c_err, c_len, w_err, w_len; tokens int32 [B, T]; token_counts int32 [B]), all on the device."""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    if input_lengths.dtype != torch.int32 or input_lengths.device != dev or input_lengths.numel() != B:
+        raise ValueError("input_lengths: expected an int32 device tensor of B elements")
+    if targets.dim() != 2 or targets.shape[0] != B or targets.dtype != torch.int32 or targets.device != dev \
+            or not targets.is_contiguous():
+        raise ValueError("targets: expected a contiguous int32 device tensor [B, Lt]")
+    if cls.dtype != torch.uint8 or cls.device != dev or cls.numel() != Cn or not cls.is_contiguous():
+        raise ValueError("cls: expected a contiguous uint8 device tensor of C = %d elements" % Cn)
+    Lt = targets.shape[1]
+    L = _lib.lib()
+    if not L.wavlm_ctc_score_supported(T, Lt):
+        raise NotImplementedError("ctc_score: T = %d frames, Lt = %d target columns is beyond the kernel's limit "
+                                  "(wavlm_ctc_score_supported: T >= 1, Lt <= 1024)" % (T, Lt))
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    token_counts = torch.empty(B, dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    need = L.wavlm_ctc_score_workspace_bytes(B, T, Lt)
+    # not ops.workspace(): a few hundred KiB a call, and a grow-only buffer kept for the life of the process would be held for
+    # a call made once per validation batch (the caching allocator hands the same block out again; launches are stream-ordered)
+    ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    check(L.wavlm_ctc_score(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(input_lengths.contiguous()), int(blank),
+                            ptr(targets) if Lt else None, Lt, int(pad), int(eos), ptr(cls), int(bool(each_token_a_word)),
+                            ptr(tokens), ptr(token_counts), ptr(counts), ptr(ws), need, stream()), "wavlm_ctc_score")
+    return counts, tokens, token_counts
