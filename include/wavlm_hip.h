@@ -786,6 +786,36 @@ int wavlm_ctc_score(const void* logits, int32_t dtype, int64_t stride_b, int64_t
                     void* workspace, uint64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC beam search with an n-gram unit LM (csrc/ctc_beam.hip; additive to ABI 30: three new symbols, nothing else changes): the
+ * lexicon-free decoder of examples/speech_recognition/w2l_decoder.py (--unit-lm, no lexicon; flashlight's LexiconFreeDecoder with
+ * the CTC criterion and log_add = false).  The rules are written out at unispeech_amd.ctc.beam_search_reference.
+ *   logits, dtype, strides, input_lengths, blank   as wavlm_ctc_greedy takes them
+ *   sil        the class that takes sil_weight (-1: none)
+ *   normalized 0: each frame's log-sum-exp is subtracted from its logits (fp32); 1: the input holds log-probabilities
+ *   lm_*       the tables of unispeech_amd.ctc_lm.NgramLM on the device: child_off int32 [lm_nodes + 1], child_word / child_logp /
+ *              child_next [lm_children] (a node's children ascending by word), node_backoff / node_suffix [lm_nodes], tok_word
+ *              int32 [C] (class -> word), lm_start the state of <s>, lm_eos_word the word </s>, lm_order 1 .. 6.  Without an LM:
+ *              lm_nodes = lm_order = 0 and the pointers are not read (one state, every LM score 0)
+ *   beam, beam_tokens, beam_threshold (>= 0, may be +inf), lm_weight, sil_weight, nbest (1 .. beam)   the decoder's options
+ *   tokens     int32 [B, nbest, T]: hypothesis h of sample b in tokens[b, h, 0 .. counts[b, h]), -1 behind it
+ *   counts     int32 [B, nbest]; scores fp32 [B, nbest] (-inf for h >= n_hyp[b]); n_hyp int32 [B]: the hypotheses returned
+ *   workspace  wavlm_ctc_beam_workspace_bytes(B, T, beam) bytes, 4-byte aligned: the back-pointers, B x T x beam int32
+ * One launch, one workgroup per sample, no global atomics; a sample's result does not depend on B or on its place in the batch.
+ * Emissions must be finite.  wavlm_ctc_beam_supported (host): 1 for 1 <= C <= 1024, 1 <= beam <= 512, beam_tokens >= 1,
+ * beam x min(beam_tokens, C) <= 16384 and 0 <= lm_order <= 6; wavlm_ctc_beam returns -1 otherwise, and for a NULL pointer, a bad
+ * view or a short workspace.  Inside that envelope nothing is truncated: the result is the reference's.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_ctc_beam_supported(int32_t C, int32_t beam, int32_t beam_tokens, int32_t lm_order);
+uint64_t wavlm_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t beam);
+int wavlm_ctc_beam(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                   const int32_t* input_lengths, int32_t blank, int32_t sil, int32_t normalized, const int32_t* lm_child_off,
+                   const int32_t* lm_child_word, const float* lm_child_logp, const int32_t* lm_child_next,
+                   const float* lm_node_backoff, const int32_t* lm_node_suffix, const int32_t* lm_tok_word, int32_t lm_nodes,
+                   int32_t lm_children, int32_t lm_start, int32_t lm_eos_word, int32_t lm_order, int32_t beam,
+                   int32_t beam_tokens, float beam_threshold, float lm_weight, float sil_weight, int32_t nbest, int32_t* tokens,
+                   int32_t* counts, float* scores, int32_t* n_hyp, void* workspace, uint64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

@@ -8,11 +8,14 @@ is the same wrapper around the other encoder) and the greedy path of src/example
   CtcCriterion    criterions/ctc.py: sum-reduced loss, ntokens / nsentences / sample_size, error counts in eval
   EncoderCtc      hubert_asr.py:138-178, 237-340 around any pre-training model of this package
   error_counts    the validation counts (unit / word edit distances) of a batch: wavlm_ctc_score (csrc/ctc_score.hip), one launch
+  beam_decode     lexicon-free beam search with an n-gram unit LM (ctc_lm.NgramLM, an ARPA file): wavlm_ctc_beam
+                  (csrc/ctc_beam.hip) on the device, beam_search_reference -- float64, the specification -- on the host
   python -m unispeech_amd.ctc decode CKPT DICT a.wav ...      one greedy transcript per file
   python -m unispeech_amd.ctc score CKPT DICT MANIFEST.tsv LABELS.ltr      UER / WER over a manifest
+  either with --lm FILE.arpa [--beam --beam-size-token --beam-threshold --lm-weight --sil-weight --nbest]: the beam search
 
-Not built, refused by name: the flashlight / KenLM decoder of the criterion (wer_kenlm_model, wer_lexicon, wer_args), reduce=False,
-and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
+Not built, refused by name: the lexicon / word-LM decoder and KenLM's binary format, the criterion's decoder options
+(wer_kenlm_model, wer_lexicon, wer_args), reduce=False, and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
 a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
 
 Tensors on the host take ctc_reference (loss) and numpy (decode): that path exists for the tests and for tiny inputs.  A device
@@ -331,8 +334,171 @@ class _IndexDictionary:
         return " ".join(str(int(t)) for t in tokens)
 
 
+# ---------------------------------------------------------------------------------------------------------- beam search
+BEAM_DEFAULTS = {"beam": 50, "beam_size_token": 100, "beam_threshold": 25.0, "lm_weight": 0.2, "sil_weight": 0.0, "nbest": 1}
+
+
+def silence_token(dictionary):
+    """W2lDecoder.__init__: <sep> if the dictionary has one, else `|`, else eos"""
+    syms = getattr(dictionary, "symbols", None)
+    if syms is None:
+        syms = list(getattr(dictionary, "indices", {}))
+    for s in ("<sep>", "|"):
+        if s in syms:
+            return int(dictionary.index(s))
+    return int(dictionary.eos())
+
+
+def _beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest):
+    beam, nbest = int(beam), int(nbest)
+    ktok = min(int(beam_size_token), int(C))
+    if beam < 1:
+        raise ValueError("beam must be at least 1")
+    if ktok < 1:
+        raise ValueError("beam_size_token must be at least 1")
+    if nbest < 1:
+        raise ValueError("nbest must be at least 1")
+    thr = float(beam_threshold)
+    if not thr >= 0.0:
+        raise ValueError("beam_threshold must not be negative")
+    for name, v in (("lm_weight", lm_weight), ("sil_weight", sil_weight)):
+        if not math.isfinite(float(v)):
+            raise ValueError("%s must be finite" % name)
+    return beam, ktok, thr, float(lm_weight), float(sil_weight), nbest
+
+
+def beam_search_reference(logits, input_lengths=None, blank=0, sil=-1, lm=None, beam=50, beam_size_token=100, beam_threshold=25.0,
+                          lm_weight=0.2, sil_weight=0.0, nbest=1, normalized=False):
+    """The lexicon-free CTC beam search in float64: the specification of wavlm_ctc_beam (csrc/ctc_beam.hip) and the host path of
+    beam_decode.  logits [T, B, C] (each frame's log-sum-exp is subtracted unless `normalized`); lm: a ctc_lm.NgramLM or None.
+
+    A hypothesis is (score, lm state, last token, prev_blank, back-pointer); the start is (0, state of <s>, none, False).
+    Frame t < input_length[b]: the min(beam_size_token, C) best classes by emission (ties to the lower class) are paired with
+    every beam entry r in rank order: s = score_r + e[t, n] (+ sil_weight if n is `sil`).  n != blank and (n != last_r or
+    prev_blank_r) is a new token: s += lm_weight * lm(state_r, n), the state advances, prev_blank = False.  n == blank keeps the
+    state, prev_blank = True.  Otherwise a repeat: the state is kept, prev_blank = False.  Candidates with equal (state, n,
+    prev_blank) merge; the best survives, and best everywhere is the total order (score descending, parent rank ascending,
+    token ascending).  Everything below best_score - beam_threshold is dropped, the first `beam` in that order are kept, and
+    that order is the next frame's rank.  At the end lm_weight * lm(state, </s>) is added, the survivors are re-ranked (ties keep
+    their rank) and the first `nbest` are returned, each as the collapse of its frame tokens.  Input length 0: one empty
+    hypothesis with the end score alone.
+
+    Returns (hyps, margin, abs_sum): per sample the list of (tokens, score); the smallest score difference that decided a
+    merge, a threshold cut, the beam boundary or the order of the returned n-best (inf if nothing was ever decided); and the
+    sum of the absolute values of the terms of the 1-best's score."""
+    x = logits.detach().to(torch.float64).cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits, dtype=np.float64)
+    T, B, C = x.shape
+    beam, ktok, thr, lmw, silw, nbest = _beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest)
+    il = [T] * B if input_lengths is None else [min(max(int(v), 0), T) for v in _host_ints(input_lengths, "input_lengths")]
+    if not 0 <= int(blank) < C:
+        raise ValueError("blank = %d is not a class" % blank)
+    if lm is not None and len(lm.tok_word) < C:
+        raise ValueError("the language model maps %d symbols, the logits have %d classes" % (len(lm.tok_word), C))
+    blank, sil = int(blank), int(sil)
+    out, margins, sums = [], [], []
+    for b in range(B):
+        e = x[:il[b], b]
+        if not normalized and il[b]:
+            m = e.max(-1, keepdims=True)
+            e = e - (m + np.log(np.exp(e - m).sum(-1, keepdims=True)))
+        if not np.isfinite(e).all():
+            raise ValueError("sample %d: the emissions must be finite" % b)
+        margin = math.inf
+        # (score, state, token, prev_blank, back = (parent's back, token) chain, abs_sum)
+        hyps = [(0.0, lm.start if lm is not None else 0, -1, False, None, 0.0)]
+        for t in range(il[b]):
+            et = e[t]
+            toks = sorted(int(c) for c in np.lexsort((np.arange(C), -et))[:ktok])
+            cands = {}
+            for r, (sc, st, tok, pb, back, ab) in enumerate(hyps):
+                for n in toks:
+                    v = float(et[n])
+                    s, a = sc + v, ab + abs(v)
+                    if n == sil:
+                        s, a = s + silw, a + abs(silw)
+                    st2 = st
+                    if n != blank and (n != tok or pb):
+                        if lm is not None:
+                            l, st2 = lm.score(st, n)
+                            s, a = s + lmw * l, a + abs(lmw * l)
+                    key = (st2, n)                                   # prev_blank is (n == blank)
+                    rank = (-s, r, n)
+                    old = cands.get(key)
+                    if old is not None:
+                        margin = min(margin, abs(old[0][0] - rank[0]))
+                    if old is None or rank < old[0]:
+                        cands[key] = (rank, (s, st2, n, n == blank, (back, n), a))
+            best = -min(v[0][0] for v in cands.values())
+            if thr != math.inf:
+                margin = min([margin] + [abs(-v[0][0] - (best - thr)) for v in cands.values()])
+            keep = sorted((v for v in cands.values() if -v[0][0] >= best - thr), key=lambda v: v[0])
+            if len(keep) > beam:
+                margin = min(margin, keep[beam - 1][1][0] - keep[beam][1][0])
+            hyps = [v[1] for v in keep[:beam]]
+        fin = []
+        for r, h in enumerate(hyps):
+            l = lmw * lm.score_eos(h[1]) if lm is not None else 0.0
+            fin.append((-(h[0] + l), r, h, h[5] + abs(l)))
+        fin.sort(key=lambda v: v[:2])
+        for i in range(min(nbest, len(fin) - 1)):
+            margin = min(margin, fin[i + 1][0] - fin[i][0])
+        res = []
+        for msc, _, h, _ in fin[:nbest]:
+            path, back = [], h[4]
+            while back is not None:
+                path.append(back[1])
+                back = back[0]
+            seq, last = [], -1
+            for a in reversed(path):
+                if a != last and a != blank:
+                    seq.append(int(a))
+                last = a
+            res.append((seq, -msc))
+        out.append(res)
+        margins.append(margin)
+        sums.append(fin[0][3])
+    return out, margins, sums
+
+
+def beam_decode(logits, input_lengths, dictionary, lm=None, beam=50, beam_size_token=100, beam_threshold=25.0, lm_weight=0.2,
+                sil_weight=0.0, nbest=1, normalized=False, blank=None):
+    """Lexicon-free CTC beam search with an optional n-gram unit LM (examples/speech_recognition/w2l_decoder.py's
+    W2lKenLMDecoder with --unit-lm and no lexicon; flashlight's LexiconFreeDecoder with log_add=False), by the rules of
+    beam_search_reference.  logits [T, B, C], either storage order; lm: a ctc_lm.NgramLM loaded with this dictionary, or None
+    (one state, every LM score 0: the 1-best is then the greedy decode).  Returns, per sample, a list of at most nbest
+    (tokens, score), best first.
+
+    Device logits take wavlm_ctc_beam (one workgroup per utterance; sizes beyond wavlm_ctc_beam_supported raise
+    NotImplementedError naming the argument, before any launch); host logits take the float64 reference.
+    Differences from flashlight, both deliberate: the search does not start from last_token = sil, and no final sil is appended
+    to the path."""
+    T, B, C = logits.shape
+    if blank is None:
+        blank = dictionary.bos()
+    sil = silence_token(dictionary)
+    if lm is not None and len(lm.tok_word) < C:
+        raise ValueError("the language model maps %d symbols, the logits have %d classes" % (len(lm.tok_word), C))
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        return beam_search_reference(logits, input_lengths, blank, sil, lm, beam, beam_size_token, beam_threshold, lm_weight,
+                                     sil_weight, nbest, normalized)[0]
+    from . import ops
+    beam, ktok, thr, lmw, silw, nbest = _beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest)
+    nbest = min(nbest, beam)
+    dev = logits.device
+    x = logits.detach().transpose(0, 1)
+    if x.shape[2] > 1 and x.stride(2) != 1:
+        x = x.contiguous()
+    if input_lengths is None:
+        il = torch.full((B,), T, dtype=torch.int32, device=dev)
+    else:
+        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    tokens, counts, scores, n_hyp = ops.ctc_beam(x, il, blank, sil, lm, beam, ktok, thr, lmw, silw, nbest, normalized)
+    tokens, counts, scores, n_hyp = tokens.cpu().numpy(), counts.cpu().numpy(), scores.cpu().numpy(), n_hyp.cpu().numpy()
+    return [[([int(v) for v in tokens[b, h, :counts[b, h]]], float(scores[b, h])) for h in range(int(n_hyp[b]))] for b in range(B)]
+
+
 # --------------------------------------------------------------------------------------------------------- error counts
-DROP, SEP, LETTER = 0, 1, 2            # the classes of wavlm_ctc_score's table (include/wavlm_hip.h)
+DROP, SEP, LETTER = 0, 1, 2           # the classes of wavlm_ctc_score's table (include/wavlm_hip.h)
 _UNSET = object()
 
 
@@ -772,7 +938,23 @@ def parse_args(argv=None):
     c.add_argument("--post-process", default="letter", choices=["letter", "none"])
     c.add_argument("--bf16", action="store_true")
     c.add_argument("--results", default=None, metavar="DIR", help="write hypo.units, hypo.word, ref.units, ref.word there")
-    return p.parse_args(argv)
+    for q in (d, c):
+        q.add_argument("--lm", default=None, metavar="FILE.arpa", help="n-gram unit LM (ARPA text): decode with the beam search")
+        q.add_argument("--beam", type=int, default=BEAM_DEFAULTS["beam"])
+        q.add_argument("--beam-size-token", type=int, default=BEAM_DEFAULTS["beam_size_token"])
+        q.add_argument("--beam-threshold", type=float, default=BEAM_DEFAULTS["beam_threshold"])
+        q.add_argument("--lm-weight", type=float, default=BEAM_DEFAULTS["lm_weight"])
+        q.add_argument("--sil-weight", type=float, default=BEAM_DEFAULTS["sil_weight"])
+        q.add_argument("--nbest", type=int, default=BEAM_DEFAULTS["nbest"])
+    a = p.parse_args(argv)
+    if a.lm is not None and a.lm.endswith((".bin", ".binary", ".trie")):
+        raise NotImplementedError("--lm %s: KenLM's binary format is not read; give the ARPA text file" % a.lm)
+    return a
+
+
+def _beam_kwargs(a):
+    return {"beam": a.beam, "beam_size_token": a.beam_size_token, "beam_threshold": a.beam_threshold, "lm_weight": a.lm_weight,
+            "sil_weight": a.sil_weight, "nbest": a.nbest}
 
 
 def read_manifest(path):
@@ -817,6 +999,13 @@ def length_batches(sizes, max_samples):
     return out
 
 
+def _load_lm(a, dictionary):
+    if a.lm is None:
+        return None
+    from .ctc_lm import NgramLM
+    return NgramLM.load(a.lm, dictionary)
+
+
 def score(a):
     """`score`: the scoring half of examples/speech_recognition/infer.py and compute_WER.py with the greedy decode"""
     from .kmeans import read_wav
@@ -829,6 +1018,7 @@ def score(a):
         model = model.to(torch.bfloat16)
     dtype = next(model.parameters()).dtype
     classes = word_classes(d, len(d), symbol)
+    lm = _load_lm(a, d)
     total = np.zeros(4, dtype=np.int64)
     hyps = [None] * len(entries)
     for batch in length_batches([n for _, n in entries], int(a.batch_seconds * 16000)):
@@ -854,8 +1044,18 @@ def score(a):
             out = model(source=src.cuda().to(dtype), padding_mask=pm.cuda() if bool(pm.any()) else None)
         logits = out["encoder_out"]
         il = None if out["padding_mask"] is None else (~out["padding_mask"]).sum(-1)
-        counts, decoded = sample_error_counts(logits, il, target, d, symbol, d.bos(), classes=classes,
-                                              hypotheses=a.results is not None)
+        if lm is not None:
+            # the beam's 1-best through the host edit distance (fusing this into wavlm_ctc_score is not built)
+            decoded = [h[0][0] if h else [] for h in beam_decode(logits, il, d, lm, **_beam_kwargs(a))]
+            counts = np.zeros((len(batch), 4), dtype=np.int64)
+            for r, (pred, i) in enumerate(zip(decoded, batch)):
+                targ = [v for v in labels[i] if v not in (d.pad(), d.eos())]
+                targ_words = post_process(d.string(targ), symbol).split()
+                pred_words = post_process(d.string(pred), symbol).split()
+                counts[r] = (edit_distance(pred, targ), len(targ), edit_distance(pred_words, targ_words), len(targ_words))
+        else:
+            counts, decoded = sample_error_counts(logits, il, target, d, symbol, d.bos(), classes=classes,
+                                                  hypotheses=a.results is not None)
         total += counts.sum(0)
         if decoded is not None:
             for i, toks in zip(batch, decoded):
@@ -887,6 +1087,8 @@ def main(argv=None):
     if a.bf16:
         model = model.to(torch.bfloat16)
     dtype = next(model.parameters()).dtype
+    lm = _load_lm(a, d)
+    symbol = None if a.post_process == "none" else "letter"
     for path in a.wavs:
         wav, sr = read_wav(path)
         if sr != 16000:
@@ -896,8 +1098,13 @@ def main(argv=None):
             x = torch.nn.functional.layer_norm(x, x.shape)
         with torch.no_grad():
             out = model(source=x.view(1, -1).to(dtype), padding_mask=None)
+        if lm is not None:                      # one line per hypothesis, best first; with --nbest above 1 the score in front
+            for toks, sc in beam_decode(out["encoder_out"], None, d, lm, **_beam_kwargs(a))[0]:
+                text = post_process(d.string(toks), symbol)
+                print(text if a.nbest == 1 else "%.4f\t%s" % (sc, text))
+            continue
         toks = greedy_decode(out["encoder_out"], None, d.bos())[0]
-        print(post_process(d.string(toks), None if a.post_process == "none" else "letter"))
+        print(post_process(d.string(toks), symbol))
     return 0
 
 

@@ -1070,3 +1070,63 @@ def ctc_score(logits, input_lengths, targets, pad, eos, blank, cls, each_token_a
                             ptr(targets) if Lt else None, Lt, int(pad), int(eos), ptr(cls), int(bool(each_token_a_word)),
                             ptr(tokens), ptr(token_counts), ptr(counts), ptr(ws), need, stream()), "wavlm_ctc_score")
     return counts, tokens, token_counts
+
+
+def ctc_beam_check_supported(C, beam, beam_tokens, lm_order):
+    """NotImplementedError naming the argument that is beyond wavlm_ctc_beam_supported; nothing is launched"""
+    L = _lib.lib()
+    C, beam, beam_tokens, lm_order = int(C), int(beam), int(beam_tokens), int(lm_order)
+    if not L.wavlm_ctc_beam_supported(C, 1, 1, 0):
+        raise NotImplementedError("ctc_beam: C = %d classes is beyond the kernel's limit (wavlm_ctc_beam_supported: C <= 1024)" % C)
+    if not L.wavlm_ctc_beam_supported(C, beam, 1, 0):
+        raise NotImplementedError("ctc_beam: beam = %d is beyond the kernel's limit (wavlm_ctc_beam_supported: 1 <= beam <= 512)"
+                                  % beam)
+    if not L.wavlm_ctc_beam_supported(C, 1, 1, lm_order):
+        raise NotImplementedError("ctc_beam: lm order = %d is beyond the kernel's limit (wavlm_ctc_beam_supported: order <= 6)"
+                                  % lm_order)
+    if not L.wavlm_ctc_beam_supported(C, beam, beam_tokens, lm_order):
+        raise NotImplementedError("ctc_beam: beam_size_token = %d with beam = %d is beyond the kernel's limit "
+                                  "(wavlm_ctc_beam_supported: beam x min(beam_size_token, C) <= 16384)" % (beam_tokens, beam))
+
+
+def ctc_beam(logits, input_lengths, blank, sil, lm, beam, beam_tokens, beam_threshold, lm_weight, sil_weight, nbest,
+             normalized=False):
+    """wavlm_ctc_beam on a [B, T, C]-indexed view (the rules of ctc_greedy): the lexicon-free beam search of every sample in one
+    launch.  lm: a ctc_lm.NgramLM (its tables are put on the device once) or None.  Returns (tokens int32 [B, nbest, T], counts
+    int32 [B, nbest], scores fp32 [B, nbest], n_hyp int32 [B]), all on the device."""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    if input_lengths.dtype != torch.int32 or input_lengths.device != dev or input_lengths.numel() != B:
+        raise ValueError("input_lengths: expected an int32 device tensor of B elements")
+    beam, beam_tokens, nbest = int(beam), int(beam_tokens), int(nbest)
+    if beam_tokens < 1:
+        raise ValueError("beam_tokens must be at least 1")
+    beam_tokens = min(beam_tokens, Cn)
+    ctc_beam_check_supported(Cn, beam, beam_tokens, lm.order if lm is not None else 0)
+    if not 1 <= nbest <= beam:
+        raise ValueError("nbest: expected 1 .. beam = %d" % beam)
+    if T < 1:
+        raise ValueError("logits: expected at least one frame")
+    if lm is not None:
+        if len(lm.tok_word) < Cn:
+            raise ValueError("lm: its symbol map has %d entries, the logits have C = %d classes" % (len(lm.tok_word), Cn))
+        t = lm.to(dev)
+        tabs = [ptr(t[k]) for k in ("child_off", "child_word", "child_logp", "child_next", "node_backoff", "node_suffix",
+                                    "tok_word")]
+        sizes = [len(lm), len(lm.child_word), int(lm.start), int(lm.eos_word), int(lm.order)]
+    else:
+        tabs, sizes = [None] * 7, [0, 0, 0, 0, 0]
+    tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+    n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    need = L.wavlm_ctc_beam_workspace_bytes(B, T, beam)
+    # not ops.workspace(), for the reason given at ctc_score: up to tens of MiB for a call made once per decoded batch
+    ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    check(L.wavlm_ctc_beam(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(input_lengths.contiguous()), int(blank), int(sil),
+                           int(bool(normalized)), *tabs, *sizes, beam, beam_tokens, float(beam_threshold), float(lm_weight),
+                           float(sil_weight), nbest, ptr(tokens), ptr(counts), ptr(scores), ptr(n_hyp), ptr(ws), need, stream()),
+          "wavlm_ctc_beam")
+    return tokens, counts, scores, n_hyp
