@@ -816,6 +816,40 @@ int wavlm_ctc_beam(const void* logits, int32_t dtype, int64_t stride_b, int64_t 
                    int32_t* counts, float* scores, int32_t* n_hyp, void* workspace, uint64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Lexicon-constrained CTC beam search with a word n-gram LM (csrc/ctc_lexbeam.hip; additive to ABI 30: three new symbols): the
+ * decoder of examples/speech_recognition/w2l_decoder.py with --lexicon (flashlight's LexiconDecoder, CTC criterion, log_add =
+ * false, SmearingMode::MAX).  The rules are written out at unispeech_amd.ctc_lexicon.lexicon_beam_search_reference.
+ *   logits .. lm_order   as wavlm_ctc_beam takes them, except that lm_tok_word is int32 [lex_words]: lexicon word id -> LM word
+ *   lex_*      the trie of unispeech_amd.ctc_lexicon.Lexicon on the device (node 0 is the root): child_off int32 [lex_nodes + 1],
+ *              child_tok / child_node int32 [lex_children] (a node's children ascending by token), node_max fp32 [lex_nodes] (the
+ *              smeared maximum of the words' scores at and below a node), label_off int32 [lex_nodes + 1], label_word int32
+ *              [lex_labels] (the words whose spelling ends at a node), lex_words the number of words, unk_word the word <unk>
+ *   lex_width  an upper bound on the candidates of one hypothesis in one frame, computed by the host from the trie
+ *   beam .. nbest   the decoder's options; word_score finite, unk_score finite or -inf (no <unk> words)
+ *   tokens, counts, scores, n_hyp   as wavlm_ctc_beam writes them
+ *   words      int32 [B, nbest, T]: the words of hypothesis h in words[b, h, 0 .. word_counts[b, h]), -1 behind them
+ *   word_counts int32 [B, nbest]
+ *   workspace  wavlm_ctc_lexbeam_workspace_bytes(B, T, beam, lex_width) bytes, 4-byte aligned
+ * One launch, one workgroup per sample, no global atomics; a sample's result does not depend on B or on its place in the batch.
+ * wavlm_ctc_lexbeam_supported (host): 1 for 1 <= C <= 1024, 1 <= beam <= 512, width >= 1, beam x width <= 16384, 0 <= lm_order
+ * <= 6 and 1 <= lex_nodes <= 2^21; wavlm_ctc_lexbeam returns -1 otherwise, and for a NULL pointer, a bad view or a short
+ * workspace.  Inside that envelope nothing is truncated: the result is the reference's.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_ctc_lexbeam_supported(int32_t C, int32_t beam, int32_t width, int32_t lm_order, int32_t lex_nodes);
+uint64_t wavlm_ctc_lexbeam_workspace_bytes(int32_t B, int32_t T, int32_t beam, int32_t width);
+int wavlm_ctc_lexbeam(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                      const int32_t* input_lengths, int32_t blank, int32_t sil, int32_t normalized, const int32_t* lm_child_off,
+                      const int32_t* lm_child_word, const float* lm_child_logp, const int32_t* lm_child_next,
+                      const float* lm_node_backoff, const int32_t* lm_node_suffix, const int32_t* lm_tok_word, int32_t lm_nodes,
+                      int32_t lm_children, int32_t lm_start, int32_t lm_eos_word, int32_t lm_order,
+                      const int32_t* lex_child_off, const int32_t* lex_child_tok, const int32_t* lex_child_node,
+                      const float* lex_node_max, const int32_t* lex_label_off, const int32_t* lex_label_word, int32_t lex_nodes,
+                      int32_t lex_children, int32_t lex_labels, int32_t lex_words, int32_t lex_width, int32_t unk_word,
+                      int32_t beam, int32_t beam_tokens, float beam_threshold, float lm_weight, float word_score, float unk_score,
+                      float sil_weight, int32_t nbest, int32_t* tokens, int32_t* counts, float* scores, int32_t* n_hyp,
+                      int32_t* words, int32_t* word_counts, void* workspace, uint64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

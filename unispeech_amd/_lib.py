@@ -230,6 +230,12 @@ SIGNATURES = {
     "wavlm_ctc_beam": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp,
                                c_vp, c_vp, c_vp, c_vp, c_u64, c_vp]),
+    "wavlm_ctc_lexbeam_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "wavlm_ctc_lexbeam_workspace_bytes": (c_u64, [c_i32, c_i32, c_i32, c_i32]),
+    "wavlm_ctc_lexbeam": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                  c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

@@ -19,7 +19,7 @@
 //   4. the block maximum gives the threshold cut; a surviving candidate is dropped if another parent's candidate of the same
 //      column has the same state and comes first in the total order (R compares per candidate, all in LDS)
 //   5. if more than R are left, the R-th largest of the 46-bit keys (score bits made monotonic, then 16383 - i) is found bit by
-//      bit, each step a block count.  Keys are unique, so the cut takes exactly R
+//      bit, each step a block count (cb_kth of ctc_beam_common.hpp, which csrc/ctc_lexbeam.hip shares).  Keys are unique, so the cut takes exactly R
 //   6. the selected candidates are compacted through an LDS counter (their slots are arbitrary) and 7. ranked by counting among
 //      themselves (their ranks are not); lane p writes beam entry rank(p) and its back-pointer (parent | token << 16) to the workspace
 // At the end lm_weight * lm(state, </s>) is added, the survivors are ranked again (ties keep their rank), and lane h < nbest walks
@@ -27,21 +27,11 @@
 // No global atomics (the two LDS counters only count); nothing depends on B or on the sample's place in the batch.  Every
 // address is formed from a range-checked id: classes are lane ids below C, states and child ranges are clamped to the table
 // sizes the caller states, back-pointers are clamped to the beam.  Emissions must be finite (a NaN score never survives a frame).
-#include "ctc_decode.hpp"
+#include "ctc_beam_common.hpp"
 #include "../../include/wavlm_hip.h"
 
-#define CB_NT 1024
-#define CB_MAXC 1024
-#define CB_MAXBEAM 512
 #define CB_MAXCAND 16384
-#define CB_MAXORDER 6
-#define CB_NONE 0xffff
-
-struct CbLm {
-  const int* child_off; const int* child_word; const float* child_logp; const int* child_next;
-  const float* node_backoff; const int* node_suffix; const int* tok_word;
-  int n_nodes, n_children, start, eos_word;
-};
+#define CB_KEYBITS 14   // CB_MAXCAND = 2^14 candidate indices
 
 static inline int cb_ktok(int64_t C, int64_t beam_tokens) { return (int)(beam_tokens < C ? beam_tokens : C); }
 static inline int cb_supported(int64_t C, int64_t beam, int64_t beam_tokens, int64_t lm_order) {
@@ -49,57 +39,6 @@ static inline int cb_supported(int64_t C, int64_t beam, int64_t beam_tokens, int
   return beam * cb_ktok(C, beam_tokens) <= CB_MAXCAND;
 }
 static inline size_t cb_lds_bytes(int R, int K, int C) { return 8 * (size_t)R * K + 16 * (size_t)R + 4 * (size_t)C + 8 * (size_t)K; }
-
-// log10 p(word | node) and the state after it
-__device__ __forceinline__ float cb_lm(const CbLm& lm, int node, int word, int* next) {
-  float acc = 0.0f;
-  for (int level = 0; level < 8; ++level) {
-    if ((unsigned)node >= (unsigned)lm.n_nodes) node = 0;
-    int lo = lm.child_off[node], hi = lm.child_off[node + 1];
-    lo = lo < 0 ? 0 : (lo > lm.n_children ? lm.n_children : lo);
-    hi = hi < lo ? lo : (hi > lm.n_children ? lm.n_children : hi);
-    const int end = hi;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (lm.child_word[mid] < word) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && lm.child_word[lo] == word) {
-      const int nx = lm.child_next[lo];
-      *next = (unsigned)nx < (unsigned)lm.n_nodes ? nx : 0;
-      return acc + lm.child_logp[lo];
-    }
-    if (node == 0) break;
-    acc += lm.node_backoff[node];
-    node = lm.node_suffix[node];
-  }
-  *next = 0;
-  return acc;
-}
-
-// the value of every lane's v combined over the workgroup, the 16 wave results in a fixed order; s_red: 16 floats
-template <bool MAX>
-__device__ __forceinline__ float cb_block(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float u = __shfl_xor(v, o, 64);
-    v = MAX ? fmaxf(v, u) : v + u;
-  }
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = s_red[0];
-#pragma unroll
-  for (int k = 1; k < CB_NT / 64; ++k) r = MAX ? fmaxf(r, s_red[k]) : r + s_red[k];
-  __syncthreads();
-  return r;
-}
-
-// 46 bits: larger = earlier in the total order (score descending, candidate index ascending); 0 = dead
-__device__ __forceinline__ unsigned long long cb_key(float s, int i) {
-  if (!(s > -INFINITY)) return 0ull;
-  unsigned u = s == 0.0f ? 0u : __float_as_uint(s);
-  u = (u >> 31) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 14) | (unsigned)(CB_MAXCAND - 1 - i);
-}
 
 __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const void* __restrict__ x, int dt, long sb, long st, int T, int C,
     const int* __restrict__ in_len, int blank, int sil, int normalized, CbLm lm, int R, int K, float thr, float lmw, float silw,
@@ -228,22 +167,10 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const void* __restrict_
     __syncthreads();
     // 5. the R-th largest key
     unsigned long long kth = 1ull;
-    if (s_cnt[0] > R) {
-      kth = 0ull;
-      for (int bit = 45; bit >= 0; --bit) {
-        const unsigned long long trial = kth | (1ull << bit);
-        int c = 0;
-        for (int i = tid; i < N; i += CB_NT) c += cb_key(cscore[i], i) >= trial ? 1 : 0;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0 && c) atomicAdd(&s_cnt[2 + (45 - bit)], c);
-        __syncthreads();
-        if (s_cnt[2 + (45 - bit)] >= R) kth = trial;
-      }
-    }
+    if (s_cnt[0] > R) kth = cb_kth<CB_KEYBITS>(cscore, N, R, s_cnt + 2);
     // 6. compaction
     for (int i = tid; i < N; i += CB_NT) {
-      const unsigned long long key = cb_key(cscore[i], i);
+      const unsigned long long key = cb_key<CB_KEYBITS>(cscore[i], i);
       if (key != 0ull && key >= kth) {
         const int slot = atomicAdd(&s_cnt[1], 1);
         if (slot < R) sel[slot] = i;
@@ -254,11 +181,11 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const void* __restrict_
     // 7. rank, the new beam and its back-pointers
     if (tid < nsel) {
       const int i = sel[tid];
-      const unsigned long long key = cb_key(cscore[i], i);
+      const unsigned long long key = cb_key<CB_KEYBITS>(cscore[i], i);
       int rank = 0;
       for (int q = 0; q < nsel; ++q) {
         const int iq = sel[q];
-        rank += cb_key(cscore[iq], iq) > key ? 1 : 0;
+        rank += cb_key<CB_KEYBITS>(cscore[iq], iq) > key ? 1 : 0;
       }
       const int r = i / K, n = ktok[i - r * K];
       bscore[rank] = cscore[i];

@@ -13,8 +13,10 @@ is the same wrapper around the other encoder) and the greedy path of src/example
   python -m unispeech_amd.ctc decode CKPT DICT a.wav ...      one greedy transcript per file
   python -m unispeech_amd.ctc score CKPT DICT MANIFEST.tsv LABELS.ltr      UER / WER over a manifest
   either with --lm FILE.arpa [--beam --beam-size-token --beam-threshold --lm-weight --sil-weight --nbest]: the beam search
+The lexicon / word-LM decoder (w2l_decoder.py with --lexicon) is unispeech_amd.ctc_lexicon, with a command line of its own:
+python -m unispeech_amd.ctc_lexicon {decode,score} ... --lexicon FILE [--lm FILE.arpa]; these two sub-commands take no lexicon.
 
-Not built, refused by name: the lexicon / word-LM decoder and KenLM's binary format, the criterion's decoder options
+Not built, refused by name: KenLM's binary format, the criterion's decoder options
 (wer_kenlm_model, wer_lexicon, wer_args), reduce=False, and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
 a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
 
@@ -920,16 +922,19 @@ def load_ctc_checkpoint(path, num_classes):
     return model.cuda().eval(), bool(ck.get("normalize", getattr(cfg, "normalize", False)))
 
 
-def parse_args(argv=None):
-    p = argparse.ArgumentParser(prog="python -m unispeech_amd.ctc", description=__doc__.split("\n\n")[0])
+def base_parser(prog, description, decode_help="greedy CTC transcripts, one line per file",
+                score_help="UER / WER of the greedy decode over a manifest (error_counts per batch)"):
+    """(parser, its `decode` sub-parser, its `score` sub-parser) with the positionals and the options that do not concern a
+    decoder; unispeech_amd.ctc_lexicon builds its command line on the same"""
+    p = argparse.ArgumentParser(prog=prog, description=description)
     sub = p.add_subparsers(dest="cmd", required=True)
-    d = sub.add_parser("decode", help="greedy CTC transcripts, one line per file")
+    d = sub.add_parser("decode", help=decode_help)
     d.add_argument("ckpt")
     d.add_argument("dict")
     d.add_argument("wavs", nargs="+")
     d.add_argument("--post-process", default="letter", choices=["letter", "none"])
     d.add_argument("--bf16", action="store_true")
-    c = sub.add_parser("score", help="UER / WER of the greedy decode over a manifest (error_counts per batch)")
+    c = sub.add_parser("score", help=score_help)
     c.add_argument("ckpt")
     c.add_argument("dict")
     c.add_argument("manifest", help="fairseq manifest: the root directory, then `relpath<TAB>nsamples` per line")
@@ -938,18 +943,30 @@ def parse_args(argv=None):
     c.add_argument("--post-process", default="letter", choices=["letter", "none"])
     c.add_argument("--bf16", action="store_true")
     c.add_argument("--results", default=None, metavar="DIR", help="write hypo.units, hypo.word, ref.units, ref.word there")
-    for q in (d, c):
-        q.add_argument("--lm", default=None, metavar="FILE.arpa", help="n-gram unit LM (ARPA text): decode with the beam search")
-        q.add_argument("--beam", type=int, default=BEAM_DEFAULTS["beam"])
-        q.add_argument("--beam-size-token", type=int, default=BEAM_DEFAULTS["beam_size_token"])
-        q.add_argument("--beam-threshold", type=float, default=BEAM_DEFAULTS["beam_threshold"])
-        q.add_argument("--lm-weight", type=float, default=BEAM_DEFAULTS["lm_weight"])
-        q.add_argument("--sil-weight", type=float, default=BEAM_DEFAULTS["sil_weight"])
-        q.add_argument("--nbest", type=int, default=BEAM_DEFAULTS["nbest"])
-    a = p.parse_args(argv)
+    return p, d, c
+
+
+def add_beam_options(q, lm_help):
+    q.add_argument("--lm", default=None, metavar="FILE.arpa", help=lm_help)
+    q.add_argument("--beam", type=int, default=BEAM_DEFAULTS["beam"])
+    q.add_argument("--beam-size-token", type=int, default=BEAM_DEFAULTS["beam_size_token"])
+    q.add_argument("--beam-threshold", type=float, default=BEAM_DEFAULTS["beam_threshold"])
+    q.add_argument("--lm-weight", type=float, default=BEAM_DEFAULTS["lm_weight"])
+    q.add_argument("--sil-weight", type=float, default=BEAM_DEFAULTS["sil_weight"])
+    q.add_argument("--nbest", type=int, default=BEAM_DEFAULTS["nbest"])
+
+
+def refuse_binary_lm(a):
     if a.lm is not None and a.lm.endswith((".bin", ".binary", ".trie")):
         raise NotImplementedError("--lm %s: KenLM's binary format is not read; give the ARPA text file" % a.lm)
     return a
+
+
+def parse_args(argv=None):
+    p, d, c = base_parser("python -m unispeech_amd.ctc", __doc__.split("\n\n")[0])
+    for q in (d, c):
+        add_beam_options(q, "n-gram unit LM (ARPA text): decode with the beam search")
+    return refuse_binary_lm(p.parse_args(argv))
 
 
 def _beam_kwargs(a):
@@ -1006,8 +1023,10 @@ def _load_lm(a, dictionary):
     return NgramLM.load(a.lm, dictionary)
 
 
-def score(a):
-    """`score`: the scoring half of examples/speech_recognition/infer.py and compute_WER.py with the greedy decode"""
+def score(a, decoder=None):
+    """`score`: the scoring half of examples/speech_recognition/infer.py and compute_WER.py with the greedy decode.
+    decoder (the command line of unispeech_amd.ctc_lexicon): (logits, input lengths, dictionary) -> per sample (tokens, words or
+    None), in place of the built-in decodes; words that are not None are the hypothesis's words as they stand (infer.py:123-124)"""
     from .kmeans import read_wav
     d = LetterDictionary.load(a.dict)
     symbol = None if a.post_process == "none" else "letter"
@@ -1018,9 +1037,12 @@ def score(a):
         model = model.to(torch.bfloat16)
     dtype = next(model.parameters()).dtype
     classes = word_classes(d, len(d), symbol)
-    lm = _load_lm(a, d)
+    lm = _load_lm(a, d) if decoder is None else None
+    if lm is not None:
+        def decoder(logits, il, d):
+            return [(h[0][0] if h else [], None) for h in beam_decode(logits, il, d, lm, **_beam_kwargs(a))]
     total = np.zeros(4, dtype=np.int64)
-    hyps = [None] * len(entries)
+    hyps, hyp_words = [None] * len(entries), [None] * len(entries)
     for batch in length_batches([n for _, n in entries], int(a.batch_seconds * 16000)):
         wavs = []
         for i in batch:
@@ -1044,15 +1066,17 @@ def score(a):
             out = model(source=src.cuda().to(dtype), padding_mask=pm.cuda() if bool(pm.any()) else None)
         logits = out["encoder_out"]
         il = None if out["padding_mask"] is None else (~out["padding_mask"]).sum(-1)
-        if lm is not None:
+        if decoder is not None:
             # the beam's 1-best through the host edit distance (fusing this into wavlm_ctc_score is not built)
-            decoded = [h[0][0] if h else [] for h in beam_decode(logits, il, d, lm, **_beam_kwargs(a))]
+            pairs = decoder(logits, il, d)
+            decoded = [pred for pred, _ in pairs]
             counts = np.zeros((len(batch), 4), dtype=np.int64)
-            for r, (pred, i) in enumerate(zip(decoded, batch)):
+            for r, ((pred, words), i) in enumerate(zip(pairs, batch)):
                 targ = [v for v in labels[i] if v not in (d.pad(), d.eos())]
                 targ_words = post_process(d.string(targ), symbol).split()
-                pred_words = post_process(d.string(pred), symbol).split()
+                pred_words = post_process(d.string(pred), symbol).split() if words is None else list(words)
                 counts[r] = (edit_distance(pred, targ), len(targ), edit_distance(pred_words, targ_words), len(targ_words))
+                hyp_words[i] = None if words is None else " ".join(words)
         else:
             counts, decoded = sample_error_counts(logits, il, target, d, symbol, d.bos(), classes=classes,
                                                   hypotheses=a.results is not None)
@@ -1069,25 +1093,25 @@ def score(a):
         for i, (hyp, ref) in enumerate(zip(hyps, labels)):          # infer.py:120-148, speaker None, id = the utterance's index
             for kind, toks in (("hypo", hyp), ("ref", ref)):
                 units = d.string(toks)
+                word = hyp_words[i] if kind == "hypo" and hyp_words[i] is not None else post_process(units, symbol)
                 files[kind + ".units"].append("%s (None-%d)" % (units, i))
-                files[kind + ".word"].append("%s (None-%d)" % (post_process(units, symbol), i))
+                files[kind + ".word"].append("%s (None-%d)" % (word, i))
         for name, lines in files.items():
             with open(os.path.join(a.results, name), "w", encoding="utf-8") as f:
                 f.write("".join(line + "\n" for line in lines))
     return 0
 
 
-def main(argv=None):
-    a = parse_args(argv)
-    if a.cmd == "score":
-        return score(a)
+def decode(a, lines=None):
+    """`decode`.  lines (the command line of unispeech_amd.ctc_lexicon): (logits of one file, dictionary) -> the lines to print
+    for it, in place of the built-in decodes"""
     from .kmeans import read_wav
     d = LetterDictionary.load(a.dict)
     model, normalize = load_ctc_checkpoint(a.ckpt, len(d))
     if a.bf16:
         model = model.to(torch.bfloat16)
     dtype = next(model.parameters()).dtype
-    lm = _load_lm(a, d)
+    lm = _load_lm(a, d) if lines is None else None
     symbol = None if a.post_process == "none" else "letter"
     for path in a.wavs:
         wav, sr = read_wav(path)
@@ -1098,6 +1122,10 @@ def main(argv=None):
             x = torch.nn.functional.layer_norm(x, x.shape)
         with torch.no_grad():
             out = model(source=x.view(1, -1).to(dtype), padding_mask=None)
+        if lines is not None:
+            for line in lines(out["encoder_out"], d):
+                print(line)
+            continue
         if lm is not None:                      # one line per hypothesis, best first; with --nbest above 1 the score in front
             for toks, sc in beam_decode(out["encoder_out"], None, d, lm, **_beam_kwargs(a))[0]:
                 text = post_process(d.string(toks), symbol)
@@ -1106,6 +1134,11 @@ def main(argv=None):
         toks = greedy_decode(out["encoder_out"], None, d.bos())[0]
         print(post_process(d.string(toks), symbol))
     return 0
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    return score(a) if a.cmd == "score" else decode(a)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,422 @@
+"""Lexicon-constrained CTC beam search with a word n-gram LM (csrc/ctc_lexbeam.hip, additive to ABI 30): the decoder of the
+reference's examples/speech_recognition/w2l_decoder.py with --lexicon -- W2lKenLMDecoder, which is flashlight's LexiconDecoder with
+the CTC criterion, log_add=False and SmearingMode.MAX -- the mode in which the letters + 4-gram word LM figures of wav2vec 2.0 /
+HuBERT / WavLM / UniSpeech fine-tuning are produced.
+
+  read_lexicon    the `load_words` file format: `word tok tok ...` per line
+  Lexicon         the trie over the spellings as flat tables, smeared with the LM's unigram-after-<s> scores; .to(device)
+  load_word_lm    an ARPA file as a ctc_lm.NgramLM over the lexicon's words
+  lexicon_beam_search_reference   float64, the specification of the kernel and the host path
+  lexicon_beam_decode             wavlm_ctc_lexbeam on the device, the reference on the host
+  python -m unispeech_amd.ctc_lexicon decode CKPT DICT a.wav ... --lexicon FILE [--lm FILE.arpa]
+  python -m unispeech_amd.ctc_lexicon score CKPT DICT MANIFEST.tsv LABELS.ltr --lexicon FILE [--lm FILE.arpa]
+  with --beam --beam-size-token --beam-threshold --lm-weight --word-score --unk-weight --sil-weight --nbest
+
+Tables (node 0 is the root; a node is a prefix of a spelling):
+  child_off  int32 [N + 1]   node v's children are child_*[child_off[v] : child_off[v + 1]]
+  child_tok  int32 [E]       the tokens that extend v, ascending within a node
+  child_node int32 [E]       the node of v + token
+  node_max   fp32  [N]       max(v): the maximum of u(w) over v's labels and of max over its children, u(w) = lm(state of <s>, w)
+  label_off  int32 [N + 1]   node v's labels are label_word[label_off[v] : label_off[v + 1]]
+  label_word int32 [L]       the words whose spelling ends at v, in word-id order
+The word LM is ctc_lm.NgramLM(order, entries, symbols=the lexicon's words): its tok_word maps a word id onto the LM's word, a
+word the LM does not list onto <unk>.
+
+Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm, time-step
+output.  The criterion's wer_lexicon / wer_kenlm_model / wer_args stay refused (ctc.CtcCriterion).
+"""
+import math
+import sys
+
+import numpy as np
+import torch
+
+from . import ctc
+from .ctc_lm import NgramLM, read_arpa
+
+MAX_LABELS = 6                       # flashlight's kTrieMaxLabel: words that may share one spelling
+UNK = "<unk>"
+
+
+def read_lexicon(path, dictionary):
+    """(words, spellings) of a lexicon file: the word strings in order of first appearance, <unk> appended if the file does not
+    list it, and [(word id, tuple of token ids)] in file order, an exact duplicate counted once.  ValueError with file:line for a
+    token that is not a symbol of the dictionary or is its unk, an empty spelling, a spelling that begins with the silence token,
+    and a seventh word for one spelling."""
+    sil = ctc.silence_token(dictionary)
+    words, wid, spellings, seen, shared = [], {}, [], set(), {}
+    with open(path, encoding="utf-8") as f:
+        lines = f.read().splitlines()
+    for no, line in enumerate(lines, 1):
+        parts = line.split()
+        if not parts:
+            continue
+
+        def bad(what):
+            return ValueError("%s:%d: %s" % (path, no, what))
+        if len(parts) == 1:
+            raise bad("the word %r has an empty spelling" % parts[0])
+        toks = []
+        for sym in parts[1:]:
+            t = int(dictionary.index(sym))
+            if t == dictionary.unk():
+                raise bad("the token %r is not a symbol of the dictionary (or is its unk)" % sym)
+            toks.append(t)
+        if toks[0] == sil:
+            raise bad("a spelling must not begin with the silence token")
+        w = wid.setdefault(parts[0], len(words))
+        if w == len(words):
+            words.append(parts[0])
+        key = (w, tuple(toks))
+        if key in seen:
+            continue
+        n = shared.get(key[1], 0) + 1
+        if n > MAX_LABELS:
+            raise bad("more than %d words share the spelling %r" % (MAX_LABELS, " ".join(parts[1:])))
+        shared[key[1]] = n
+        seen.add(key)
+        spellings.append(key)
+    if UNK not in wid:
+        words.append(UNK)
+    return words, spellings
+
+
+def load_word_lm(path, words):
+    """the ARPA file as an NgramLM whose symbol map is over the lexicon's words"""
+    order, entries = read_arpa(path)
+    return NgramLM(order, entries, list(words))
+
+
+class Lexicon:
+    """The trie and its smearing on the host; .to(device) gives the torch tensors the kernel takes."""
+
+    def __init__(self, words, spellings, dictionary, lm=None):
+        """words: the word strings, one per word id, <unk> among them; spellings: [(word id, token ids)]; lm: an NgramLM built
+        with symbols=words, or None (every u(w) is 0)"""
+        self.words, self.lm = list(words), lm
+        if UNK not in self.words:
+            raise ValueError("the lexicon's words must hold %s" % UNK)
+        if lm is not None and len(lm.tok_word) != len(self.words):
+            raise ValueError("the language model maps %d symbols, the lexicon has %d words" % (len(lm.tok_word), len(self.words)))
+        self.unk_word = self.words.index(UNK)
+        self.sil = ctc.silence_token(dictionary)
+        C = len(dictionary)
+        kids, labels = [{}], [[]]
+        for w, toks in sorted(set((int(w), tuple(int(t) for t in toks)) for w, toks in spellings)):
+            if not 0 <= w < len(self.words):
+                raise ValueError("word id %d is not one of the %d words" % (w, len(self.words)))
+            if not toks:
+                raise ValueError("the word %r has an empty spelling" % self.words[w])
+            if toks[0] == self.sil:
+                raise ValueError("the spelling of %r begins with the silence token" % self.words[w])
+            v = 0
+            for t in toks:
+                if not 0 <= t < C or t == dictionary.unk():
+                    raise ValueError("the token %d in the spelling of %r is not a symbol of the dictionary" % (t, self.words[w]))
+                if t not in kids[v]:
+                    kids[v][t] = len(kids)
+                    kids.append({})
+                    labels.append([])
+                v = kids[v][t]
+            labels[v].append(w)
+            if len(labels[v]) > MAX_LABELS:
+                raise ValueError("more than %d words share the spelling of %r" % (MAX_LABELS, self.words[w]))
+        self.word_unigram = np.asarray([lm.score_word(lm.start, int(lm.tok_word[w]))[0] if lm is not None else 0.0
+                                        for w in range(len(self.words))], dtype=np.float64)
+        n = len(kids)
+        node_max = np.full(n, -math.inf)
+        for v in range(n - 1, -1, -1):                 # a child is created after its parent: descending ids see children first
+            m = max([self.word_unigram[w] for w in labels[v]] + [node_max[c] for c in kids[v].values()], default=-math.inf)
+            node_max[v] = m
+        if n == 1:
+            node_max[0] = 0.0
+        co, ct, cn, lo, lw = [0], [], [], [0], []
+        for v in range(n):
+            for t in sorted(kids[v]):
+                ct.append(t)
+                cn.append(kids[v][t])
+            co.append(len(ct))
+            lw += sorted(labels[v])
+            lo.append(len(lw))
+        self.child_off = np.asarray(co, dtype=np.int32)
+        self.child_tok = np.asarray(ct, dtype=np.int32)
+        self.child_node = np.asarray(cn, dtype=np.int32)
+        self.node_max = node_max
+        self.label_off = np.asarray(lo, dtype=np.int32)
+        self.label_word = np.asarray(lw, dtype=np.int32)
+        nlab = np.diff(self.label_off)
+        nkid = np.diff(self.child_off)
+        self.max_labels = int(nlab.max()) if n else 0
+        # the candidates a child can give its parent: a descent if it has children, a word per label (or <unk>, if those are on)
+        self.max_node_candidates = {}
+        for unk in (False, True):
+            per_child = (nkid > 0).astype(np.int64) + np.maximum(nlab, 1 if unk else 0)
+            csum = np.concatenate([[0], np.cumsum(per_child[self.child_node])])
+            self.max_node_candidates[unk] = int((csum[self.child_off[1:]] - csum[self.child_off[:-1]]).max())
+        self._dev = {}
+
+    @classmethod
+    def load(cls, path, dictionary, lm_path=None):
+        """the lexicon file, and the ARPA file if there is one, as a Lexicon (its .lm is the word LM)"""
+        words, spellings = read_lexicon(path, dictionary)
+        return cls(words, spellings, dictionary, load_word_lm(lm_path, words) if lm_path is not None else None)
+
+    def __len__(self):
+        return len(self.node_max)
+
+    def width(self, ktok, unk=False):
+        """an upper bound on the candidates of one hypothesis in one frame with `ktok` considered classes, with or without <unk>
+        words: the children among them, each with a descent and its labels, or the fullest node of this trie, plus blank, repeat
+        and root silence"""
+        unk = bool(unk)
+        return min(int(ktok) * (1 + max(self.max_labels, 1 if unk else 0)), self.max_node_candidates[unk]) + 3
+
+    def child(self, v, t):
+        lo, hi = int(self.child_off[v]), int(self.child_off[v + 1])
+        k = lo + int(np.searchsorted(self.child_tok[lo:hi], t))
+        return int(self.child_node[k]) if k < hi and self.child_tok[k] == t else -1
+
+    def labels(self, v):
+        return [int(w) for w in self.label_word[self.label_off[v]:self.label_off[v + 1]]]
+
+    def to(self, device):
+        """the tables as contiguous torch tensors on `device` (built once per device): a dict of the names above"""
+        key = str(device)
+        if key not in self._dev:
+            def t(a, dtype):
+                a = np.ascontiguousarray(a, dtype=dtype)
+                if a.size == 0:
+                    a = np.zeros(1, dtype=dtype)
+                return torch.from_numpy(a).to(device)
+            self._dev[key] = {"child_off": t(self.child_off, np.int32), "child_tok": t(self.child_tok, np.int32),
+                              "child_node": t(self.child_node, np.int32), "node_max": t(self.node_max, np.float32),
+                              "label_off": t(self.label_off, np.int32), "label_word": t(self.label_word, np.int32)}
+        return self._dev[key]
+
+
+def _lex_options(word_score, unk_weight):
+    ws, us = float(word_score), float(unk_weight)
+    if not math.isfinite(ws):
+        raise ValueError("word_score must be finite")
+    if not (math.isfinite(us) or us == -math.inf):
+        raise ValueError("unk_weight must be finite or -inf")
+    return ws, us
+
+
+def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-1, beam=50, beam_size_token=100,
+                                  beam_threshold=25.0, lm_weight=0.2, word_score=1.0, unk_weight=-math.inf, sil_weight=0.0,
+                                  nbest=1, normalized=False):
+    """The lexicon-constrained CTC beam search in float64: the specification of wavlm_ctc_lexbeam (csrc/ctc_lexbeam.hip) and the
+    host path of lexicon_beam_decode.  logits [T, B, C] (each frame's log-sum-exp is subtracted unless `normalized`); the LM is
+    lexicon.lm (None: every LM score 0).
+
+    A hypothesis is (score, lm state, trie node, last token, prev_blank, back-pointer); the start is (0, state of <s>, root,
+    none, False).  Frame t < input_length[b]: the considered classes are the min(beam_size_token, C) best by emission (ties to
+    the lower class).  A candidate of beam entry r with token n has s = score_r + e[t, n] (+ sil_weight if n is `sil`) and is one of
+      1. n == blank, always tried: same state and node, prev_blank = True
+      2. n == last_r, not prev_blank_r, last_r not none -- a repeat, always tried: same state and node, prev_blank = False
+      3. node_r is the root and n == sil (and 2 does not apply), always tried: silence between words, stays at the root
+      4. otherwise n must be considered and node_r must have a child c at n.  Slot 0, if c has children: (state_r, c) with
+         s + lm_weight * (max(c) - lexmax(node_r)).  Slot 1 + k for the k-th label w of c: (state after w, root) with
+         s + lm_weight * (lm(state_r, w) - lexmax(node_r)) + word_score; the back-pointer records w
+      5. c has no label and unk_weight > -inf: slot 1 with the word <unk> and unk_weight in place of word_score
+    where lexmax(root) = 0 and lexmax(v) = max(v) (the smearing: over a word the terms telescope to lm(state, w), so only the
+    pruning depends on them).  Candidates with equal (state, node, token, prev_blank) merge; the best survives, and best
+    everywhere is the total order (score descending, parent rank ascending, token ascending, slot ascending).  Everything below
+    best_score - beam_threshold is dropped, the first `beam` in that order are kept, and that order is the next frame's rank.  At
+    the end only the survivors at the root finish if there is one, else all; lm_weight * lm(state, </s>) is added, they are
+    re-ranked (ties keep their rank) and the first `nbest` are returned.  Input length 0: one empty hypothesis, the end score.
+
+    Differences from flashlight's LexiconDecoder, all deliberate: (1) the search does not start from last_token = sil and no
+    final sil is appended, as in the lexicon-free search; (2) a word is completed only by a new token -- flashlight runs its
+    label loop outside the CTC new-token test and patches the root with a `continue`; the rule above is the CTC-correct one and
+    makes the search with an unbounded beam equal the maximum over all frame paths and their parses; (3) a repeat is allowed at
+    every node, flashlight offers only sil at the root.
+
+    Returns (hyps, margin, abs_sum): per sample the list of (words, tokens, score), words as ids; the smallest score difference
+    that decided a merge, a threshold cut, the beam boundary or the order of the returned n-best (inf if nothing was decided);
+    and the sum of the absolute values of the terms of the 1-best's score."""
+    x = logits.detach().to(torch.float64).cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits, dtype=np.float64)
+    T, B, C = x.shape
+    beam, ktok, thr, lmw, silw, nbest = ctc._beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest)
+    wsc, usc = _lex_options(word_score, unk_weight)
+    il = [T] * B if input_lengths is None else [min(max(int(v), 0), T) for v in ctc._host_ints(input_lengths, "input_lengths")]
+    if not 0 <= int(blank) < C:
+        raise ValueError("blank = %d is not a class" % blank)
+    if len(lexicon.child_tok) and int(lexicon.child_tok.max()) >= C:
+        raise ValueError("the lexicon spells with token %d, the logits have %d classes" % (int(lexicon.child_tok.max()), C))
+    blank, sil = int(blank), int(sil)
+    lx, lm = lexicon, lexicon.lm
+    nmax = lx.node_max
+    has_kids = np.diff(lx.child_off) > 0
+
+    def lm_word(st, w):
+        return lm.score_word(st, int(lm.tok_word[w])) if lm is not None else (0.0, st)
+    out, margins, sums = [], [], []
+    for b in range(B):
+        e = x[:il[b], b]
+        if not normalized and il[b]:
+            m = e.max(-1, keepdims=True)
+            e = e - (m + np.log(np.exp(e - m).sum(-1, keepdims=True)))
+        if not np.isfinite(e).all():
+            raise ValueError("sample %d: the emissions must be finite" % b)
+        margin = math.inf
+        # (score, state, node, token, prev_blank, back = (parent's back, token, word or -1) chain, abs_sum)
+        hyps = [(0.0, lm.start if lm is not None else 0, 0, -1, False, None, 0.0)]
+        for t in range(il[b]):
+            et = e[t]
+            considered = set(int(c) for c in np.lexsort((np.arange(C), -et))[:ktok])
+            cands = {}
+
+            def put(r, n, slot, s, a, st, nd, word, back):
+                nonlocal margin
+                key, rank = (st, nd, n), (-s, r, n, slot)           # prev_blank is (n == blank)
+                old = cands.get(key)
+                if old is not None:
+                    margin = min(margin, abs(old[0][0] - rank[0]))
+                if old is None or rank < old[0]:
+                    cands[key] = (rank, (s, st, nd, n, n == blank, (back, n, word), a))
+            for r, (sc, st, nd, tok, pb, back, ab) in enumerate(hyps):
+                lexmax = 0.0 if nd == 0 else float(nmax[nd])
+                tried = set(considered)
+                tried.add(blank)
+                if tok >= 0 and not pb:
+                    tried.add(tok)
+                if nd == 0 and 0 <= sil < C:
+                    tried.add(sil)
+                for n in sorted(tried):
+                    v = float(et[n])
+                    s, a = sc + v, ab + abs(v)
+                    if n == sil:
+                        s, a = s + silw, a + abs(silw)
+                    if n == blank or (n == tok and not pb) or (nd == 0 and n == sil):       # kinds 1, 2, 3
+                        put(r, n, 0, s, a, st, nd, -1, back)
+                        continue
+                    c = lx.child(nd, n) if n in considered else -1
+                    if c < 0:
+                        continue
+                    if has_kids[c]:
+                        d = lmw * (float(nmax[c]) - lexmax)
+                        put(r, n, 0, s + d, a + abs(d), st, c, -1, back)
+                    labs = lx.labels(c)
+                    if labs:
+                        for k, w in enumerate(labs):
+                            l, st2 = lm_word(st, w)
+                            d = lmw * (l - lexmax)
+                            put(r, n, 1 + k, s + d + wsc, a + abs(d) + abs(wsc), st2, 0, w, back)
+                    elif usc > -math.inf:
+                        l, st2 = lm_word(st, lx.unk_word)
+                        d = lmw * (l - lexmax)
+                        put(r, n, 1, s + d + usc, a + abs(d) + abs(usc), st2, 0, lx.unk_word, back)
+            best = -min(v[0][0] for v in cands.values())
+            if thr != math.inf:
+                margin = min([margin] + [abs(-v[0][0] - (best - thr)) for v in cands.values()])
+            keep = sorted((v for v in cands.values() if -v[0][0] >= best - thr), key=lambda v: v[0])
+            if len(keep) > beam:
+                margin = min(margin, keep[beam - 1][1][0] - keep[beam][1][0])
+            hyps = [v[1] for v in keep[:beam]]
+        if any(h[2] == 0 for h in hyps):
+            hyps_fin = [(r, h) for r, h in enumerate(hyps) if h[2] == 0]
+        else:
+            hyps_fin = list(enumerate(hyps))
+        fin = []
+        for r, h in hyps_fin:
+            l = lmw * lm.score_eos(h[1]) if lm is not None else 0.0
+            fin.append((-(h[0] + l), r, h, h[6] + abs(l)))
+        fin.sort(key=lambda v: v[:2])
+        for i in range(min(nbest, len(fin) - 1)):
+            margin = min(margin, fin[i + 1][0] - fin[i][0])
+        res = []
+        for msc, _, h, _ in fin[:nbest]:
+            path, wds, back = [], [], h[5]
+            while back is not None:
+                path.append(back[1])
+                if back[2] >= 0:
+                    wds.append(int(back[2]))
+                back = back[0]
+            seq, last = [], -1
+            for a in reversed(path):
+                if a != last and a != blank:
+                    seq.append(int(a))
+                last = a
+            res.append((wds[::-1], seq, -msc))
+        out.append(res)
+        margins.append(margin)
+        sums.append(fin[0][3])
+    return out, margins, sums
+
+
+def lexicon_beam_decode(logits, input_lengths, dictionary, lexicon, lm=None, beam=50, beam_size_token=100, beam_threshold=25.0,
+                        lm_weight=0.2, word_score=1.0, unk_weight=-math.inf, sil_weight=0.0, nbest=1, normalized=False,
+                        blank=None):
+    """Lexicon-constrained CTC beam search with an optional word n-gram LM, by the rules of lexicon_beam_search_reference.
+    logits [T, B, C], either storage order; lexicon: a Lexicon over this dictionary; lm: the NgramLM the lexicon was built with
+    (lexicon.lm), or None for a lexicon without one.  Returns, per sample, a list of at most nbest (word strings, tokens, score),
+    best first.
+
+    Device logits take wavlm_ctc_lexbeam (one workgroup per utterance; sizes beyond wavlm_ctc_lexbeam_supported raise
+    NotImplementedError naming the argument, before any launch); host logits take the float64 reference."""
+    T, B, C = logits.shape
+    if blank is None:
+        blank = dictionary.bos()
+    if lm is not lexicon.lm:
+        raise ValueError("lm must be the language model the lexicon was built with (lexicon.lm): the trie is smeared with it")
+    sil = ctc.silence_token(dictionary)
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        hyps = lexicon_beam_search_reference(logits, input_lengths, lexicon, blank, sil, beam, beam_size_token, beam_threshold,
+                                             lm_weight, word_score, unk_weight, sil_weight, nbest, normalized)[0]
+        return [[([lexicon.words[w] for w in wds], toks, sc) for wds, toks, sc in h] for h in hyps]
+    from . import ops
+    beam, ktok, thr, lmw, silw, nbest = ctc._beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest)
+    wsc, usc = _lex_options(word_score, unk_weight)
+    nbest = min(nbest, beam)
+    dev = logits.device
+    x = logits.detach().transpose(0, 1)
+    if x.shape[2] > 1 and x.stride(2) != 1:
+        x = x.contiguous()
+    if input_lengths is None:
+        il = torch.full((B,), T, dtype=torch.int32, device=dev)
+    else:
+        il = torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    res = ops.ctc_lexbeam(x, il, blank, sil, lexicon, beam, ktok, thr, lmw, wsc, usc, silw, nbest, normalized)
+    tokens, counts, scores, n_hyp, words, wcounts = (v.cpu().numpy() for v in res)
+    return [[([lexicon.words[int(w)] for w in words[b, h, :wcounts[b, h]]], [int(v) for v in tokens[b, h, :counts[b, h]]],
+              float(scores[b, h])) for h in range(int(n_hyp[b]))] for b in range(B)]
+
+
+# ---------------------------------------------------------------------------------------------------------- command line
+def parse_args(argv=None):
+    p, d, c = ctc.base_parser("python -m unispeech_amd.ctc_lexicon", __doc__.split("\n\n")[0],
+                              "word transcripts of the lexicon beam search, one line per file",
+                              "UER / WER of the lexicon beam search over a manifest")
+    for q in (d, c):
+        q.add_argument("--lexicon", required=True, metavar="FILE", help="`word tok tok ...` per line")
+        ctc.add_beam_options(q, "n-gram word LM (ARPA text) over the lexicon's words")
+        q.add_argument("--word-score", type=float, default=1.0)
+        q.add_argument("--unk-weight", type=float, default=-math.inf)
+    return ctc.refuse_binary_lm(p.parse_args(argv))
+
+
+def _options(a):
+    return dict(ctc._beam_kwargs(a), word_score=a.word_score, unk_weight=a.unk_weight)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    d = ctc.LetterDictionary.load(a.dict)
+    lexicon = Lexicon.load(a.lexicon, d, a.lm)
+    kw = _options(a)
+    if a.cmd == "score":
+        def decoder(logits, il, d):
+            return [(h[0][1], h[0][0]) if h else ([], []) for h in lexicon_beam_decode(logits, il, d, lexicon, lexicon.lm, **kw)]
+        return ctc.score(a, decoder)
+
+    def lines(logits, d):                       # one line per hypothesis, best first; with --nbest above 1 the score in front
+        for words, _, sc in lexicon_beam_decode(logits, None, d, lexicon, lexicon.lm, **kw)[0]:
+            text = " ".join(words)
+            yield text if a.nbest == 1 else "%.4f\t%s" % (sc, text)
+    return ctc.decode(a, lines)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -5,6 +5,7 @@ below ends in exactly one (or a fixed short sequence of) libwavlm_hip.so entry p
 a CPU tensor raises.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -1130,3 +1131,91 @@ def ctc_beam(logits, input_lengths, blank, sil, lm, beam, beam_tokens, beam_thre
                            float(sil_weight), nbest, ptr(tokens), ptr(counts), ptr(scores), ptr(n_hyp), ptr(ws), need, stream()),
           "wavlm_ctc_beam")
     return tokens, counts, scores, n_hyp
+
+
+def ctc_lexbeam_max_beam(C, width, lm_order, lex_nodes):
+    """the largest beam wavlm_ctc_lexbeam_supported admits for these sizes (0: none), found by probing it"""
+    ok = _lib.lib().wavlm_ctc_lexbeam_supported
+    lo, hi = 0, 1 << 20                    # supported(lo) (or lo = 0), not supported(hi); support is monotone in the beam
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ok(int(C), mid, int(width), int(lm_order), int(lex_nodes)):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def ctc_lexbeam_check_supported(C, beam, width, lm_order, lex_nodes):
+    """NotImplementedError naming the argument that is beyond wavlm_ctc_lexbeam_supported; nothing is launched"""
+    L = _lib.lib()
+    C, beam, width, lm_order, lex_nodes = int(C), int(beam), int(width), int(lm_order), int(lex_nodes)
+    ok = L.wavlm_ctc_lexbeam_supported
+    if not ok(C, 1, 1, 0, 1):
+        raise NotImplementedError("ctc_lexbeam: C = %d classes is beyond the kernel's limit (wavlm_ctc_lexbeam_supported: C <= 1024)"
+                                  % C)
+    if not ok(C, beam, 1, 0, 1):
+        raise NotImplementedError("ctc_lexbeam: beam = %d is beyond the kernel's limit (wavlm_ctc_lexbeam_supported: 1 <= beam <= "
+                                  "512)" % beam)
+    if not ok(C, 1, 1, lm_order, 1):
+        raise NotImplementedError("ctc_lexbeam: lm order = %d is beyond the kernel's limit (wavlm_ctc_lexbeam_supported: order <= "
+                                  "6)" % lm_order)
+    if not ok(C, 1, 1, 0, lex_nodes):
+        raise NotImplementedError("ctc_lexbeam: lexicon of %d trie nodes is beyond the kernel's limit "
+                                  "(wavlm_ctc_lexbeam_supported: nodes <= 2^21)" % lex_nodes)
+    if not ok(C, beam, width, lm_order, lex_nodes):
+        raise NotImplementedError("ctc_lexbeam: beam = %d with this lexicon and beam_size_token (at most %d candidates per "
+                                  "hypothesis and frame) is beyond the kernel's limit (wavlm_ctc_lexbeam_supported admits beam <= "
+                                  "%d here)" % (beam, width, ctc_lexbeam_max_beam(C, width, lm_order, lex_nodes)))
+
+
+def ctc_lexbeam(logits, input_lengths, blank, sil, lexicon, beam, beam_tokens, beam_threshold, lm_weight, word_score, unk_score,
+                sil_weight, nbest, normalized=False):
+    """wavlm_ctc_lexbeam on a [B, T, C]-indexed view (the rules of ctc_greedy): the lexicon-constrained beam search of every
+    sample in one launch.  lexicon: a ctc_lexicon.Lexicon (its tables and those of its .lm are put on the device once).  Returns
+    (tokens int32 [B, nbest, T], counts int32 [B, nbest], scores fp32 [B, nbest], n_hyp int32 [B], words int32 [B, nbest, T],
+    word_counts int32 [B, nbest]), all on the device."""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    if input_lengths.dtype != torch.int32 or input_lengths.device != dev or input_lengths.numel() != B:
+        raise ValueError("input_lengths: expected an int32 device tensor of B elements")
+    beam, beam_tokens, nbest = int(beam), int(beam_tokens), int(nbest)
+    if beam_tokens < 1:
+        raise ValueError("beam_tokens must be at least 1")
+    beam_tokens = min(beam_tokens, Cn)
+    lm = lexicon.lm
+    width = lexicon.width(beam_tokens, float(unk_score) > -math.inf)
+    ctc_lexbeam_check_supported(Cn, beam, width, lm.order if lm is not None else 0, len(lexicon))
+    if not 1 <= nbest <= beam:
+        raise ValueError("nbest: expected 1 .. beam = %d" % beam)
+    if T < 1:
+        raise ValueError("logits: expected at least one frame")
+    if len(lexicon.child_tok) and int(lexicon.child_tok.max()) >= Cn:
+        raise ValueError("lexicon: it spells with token %d, the logits have C = %d classes" % (int(lexicon.child_tok.max()), Cn))
+    if lm is not None:
+        t = lm.to(dev)
+        tabs = [ptr(t[k]) for k in ("child_off", "child_word", "child_logp", "child_next", "node_backoff", "node_suffix",
+                                    "tok_word")]
+        sizes = [len(lm), len(lm.child_word), int(lm.start), int(lm.eos_word), int(lm.order)]
+    else:
+        tabs, sizes = [None] * 7, [0, 0, 0, 0, 0]
+    x = lexicon.to(dev)
+    ltabs = [ptr(x[k]) for k in ("child_off", "child_tok", "child_node", "node_max", "label_off", "label_word")]
+    lsizes = [len(lexicon), len(lexicon.child_tok), len(lexicon.label_word), len(lexicon.words), width, int(lexicon.unk_word)]
+    tokens = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+    words = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+    word_counts = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+    n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    need = L.wavlm_ctc_lexbeam_workspace_bytes(B, T, beam, width)
+    # not ops.workspace(), for the reason given at ctc_score
+    ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    check(L.wavlm_ctc_lexbeam(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(input_lengths.contiguous()), int(blank), int(sil),
+                              int(bool(normalized)), *tabs, *sizes, *ltabs, *lsizes, beam, beam_tokens, float(beam_threshold),
+                              float(lm_weight), float(word_score), float(unk_score), float(sil_weight), nbest, ptr(tokens),
+                              ptr(counts), ptr(scores), ptr(n_hyp), ptr(words), ptr(word_counts), ptr(ws), need, stream()),
+          "wavlm_ctc_lexbeam")
+    return tokens, counts, scores, n_hyp, words, word_counts
