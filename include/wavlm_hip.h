@@ -850,6 +850,41 @@ int wavlm_ctc_lexbeam(const void* logits, int32_t dtype, int64_t stride_b, int64
                       int32_t* words, int32_t* word_counts, void* workspace, uint64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CTC forced alignment (csrc/ctc_align.hip; additive to ABI 30: three new symbols, nothing else changes): the best path of a
+ * transcript through the emissions -- which frames belong to which label -- and from it the `timesteps` of
+ * examples/speech_recognition/w2l_decoder.py:243-262.  The rules are written out at
+ * unispeech_amd.ctc_align.forced_align_reference; the path is that float64 restatement's bit for bit (the recursion runs on the
+ * raw logits in float64: max is exact and every value is one addition of the same two operands on both sides).
+ *   logits, dtype, strides, targets, target_offsets, n_targets, Lmax, input_lengths, blank   exactly as wavlm_ctc_loss takes them;
+ *            any C >= 1, and rows at or beyond a sample's input length are never read
+ *   frames   int32 [B, T]: the index j in [0, L) of the label that frame t emits, -1 for a blank frame, -2 for t >= input length
+ *   spans    int32 [B, Lmax, 2]: first frame and one-past-last frame of label j; -1 for j >= L
+ *   token_scores fp32 [B, Lmax]: the sum of lp[t, l_j] over the label's frames, lp = logits - row log-sum-exp, added in
+ *            ascending t in float64 and rounded once; 0 for j >= L
+ *   score    fp32 [B]: the sum of lp over all frames of the path, in ascending t, float64, rounded once
+ *   workspace  wavlm_ctc_align_workspace_bytes(B, T, Lmax) bytes, 16-byte aligned: uint64 [B, 4] clock stamps in front (100 MHz
+ *            ticks at the sample's start, after the forward pass, after the back-trace and at its end -- tools/ctc_align_bench.py
+ *            reads them), the row log-sum-exp in float64, and the back-pointers, 2 bits per (b, t, s) in 16-byte groups of 64
+ *            positions
+ * Ties: among equal predecessors the one with the larger s wins (stay over s - 1 over s - 2), and at the end S - 1 wins over
+ * S - 2: of all best paths, the one whose state sequence read from the last frame to the first is lexicographically greatest.
+ * Special cases: no alignment exists (the input length is below L + the number of adjacent equal labels): score -inf, frames -2
+ * throughout, spans -1, token_scores 0.  Input length 0: score 0 for L = 0, -inf otherwise.  An offset or a label out of range:
+ * score NaN, the rest as without an alignment (wavlm_ctc_loss treats such a sample the same way).
+ * Two launches (row log-sum-exp; forward, back-trace and sums by one workgroup per sample), no global atomics; a sample's result
+ * does not depend on B or on its place in the batch.  The back-trace reads the back-pointers from LDS, staged
+ * WAVLM_CTC_ALIGN_BLOCK frames at a time.  wavlm_ctc_align_supported (host): 1 for 0 <= Lmax <= 1023; wavlm_ctc_align returns -1
+ * otherwise, and for a NULL pointer, a bad view or a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define WAVLM_CTC_ALIGN_BLOCK 32
+int wavlm_ctc_align_supported(int32_t Lmax);
+uint64_t wavlm_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
+int wavlm_ctc_align(const void* logits, int32_t dtype, int64_t stride_b, int64_t stride_t, int32_t B, int32_t T, int32_t C,
+                    const int32_t* targets, const int32_t* target_offsets, int32_t n_targets, int32_t Lmax,
+                    const int32_t* input_lengths, int32_t blank, int32_t* frames, int32_t* spans, float* token_scores,
+                    float* score, void* workspace, uint64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

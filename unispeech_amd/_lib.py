@@ -236,6 +236,10 @@ SIGNATURES = {
                                   c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
                                   c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp,
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64, c_vp]),
+    "wavlm_ctc_align_supported": (c_i32, [c_i32]),
+    "wavlm_ctc_align_workspace_bytes": (c_u64, [c_i32, c_i32, c_i32]),
+    "wavlm_ctc_align": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

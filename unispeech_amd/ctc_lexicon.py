@@ -22,8 +22,8 @@ Tables (node 0 is the root; a node is a prefix of a spelling):
 The word LM is ctc_lm.NgramLM(order, entries, symbols=the lexicon's words): its tok_word maps a word id onto the LM's word, a
 word the LM does not list onto <unk>.
 
-Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm, time-step
-output.  The criterion's wer_lexicon / wer_kenlm_model / wer_args stay refused (ctc.CtcCriterion).
+Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm.  (Time
+steps: ctc_align.timesteps aligns a hypothesis's tokens.)  The criterion's wer_lexicon / wer_kenlm_model / wer_args stay refused (ctc.CtcCriterion).
 """
 import math
 import sys

@@ -1073,6 +1073,44 @@ def ctc_score(logits, input_lengths, targets, pad, eos, blank, cls, each_token_a
     return counts, tokens, token_counts
 
 
+def ctc_align_check_supported(Lmax):
+    """NotImplementedError naming the value that is beyond wavlm_ctc_align_supported; nothing is launched"""
+    if not _lib.lib().wavlm_ctc_align_supported(int(Lmax)):
+        raise NotImplementedError("ctc_align: L = %d labels in one target is beyond the kernel's limit "
+                                  "(wavlm_ctc_align_supported: L <= 1023)" % Lmax)
+
+
+def ctc_align(logits, targets, target_offsets, n_targets, Lmax, input_lengths, blank, ws=None):
+    """wavlm_ctc_align on a [B, T, C]-indexed view (the rules of ctc_loss_fwd_bwd for logits, targets, target_offsets and
+    input_lengths).  Returns (frames int32 [B, T], spans int32 [B, Lmax, 2], token_scores fp32 [B, Lmax], score fp32 [B]) on the
+    device.  ws (optional): a uint8 device tensor to use as the workspace -- it starts with the kernel's uint64 [B, 4] clock
+    stamps, which tools/ctc_align_bench.py reads."""
+    dev = _dev(logits)
+    sb, st = _ctc_view(logits)
+    B, T, Cn = logits.shape
+    Lmax = int(Lmax)
+    ctc_align_check_supported(Lmax)
+    for name, t, n in (("targets", targets, n_targets), ("target_offsets", target_offsets, B + 1),
+                       ("input_lengths", input_lengths, B)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < n:
+            raise ValueError("%s: expected a contiguous int32 device tensor of at least %d elements" % (name, n))
+    frames = torch.empty((B, T), dtype=torch.int32, device=dev)
+    spans = torch.empty((B, Lmax, 2), dtype=torch.int32, device=dev)
+    token_scores = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    need = L.wavlm_ctc_align_workspace_bytes(B, T, Lmax)
+    if ws is None:
+        # not ops.workspace(), for the reason given at ctc_score
+        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous():
+        raise ValueError("ws: expected a contiguous uint8 device tensor")
+    check(L.wavlm_ctc_align(ptr(logits), dt(logits), sb, st, B, T, Cn, ptr(targets) if n_targets else None, ptr(target_offsets),
+                            int(n_targets), Lmax, ptr(input_lengths), int(blank), ptr(frames), ptr(spans) if Lmax else None,
+                            ptr(token_scores) if Lmax else None, ptr(score), ptr(ws), ws.numel(), stream()), "wavlm_ctc_align")
+    return frames, spans, token_scores, score
+
+
 def ctc_beam_check_supported(C, beam, beam_tokens, lm_order):
     """NotImplementedError naming the argument that is beyond wavlm_ctc_beam_supported; nothing is launched"""
     L = _lib.lib()
