@@ -885,6 +885,45 @@ int wavlm_ctc_align(const void* logits, int32_t dtype, int64_t stride_b, int64_t
                     float* score, void* workspace, uint64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Transformer LM (csrc/lm.hip; additive to ABI 30: five new symbols, nothing else changes): the two steps of an inference pass of
+ * the reference's decoder-only TransformerDecoder (src/fairseq/models/transformer.py:636-991, as TransformerLanguageModel builds
+ * it) that no other entry point covers.  Its Linear layers are wavlm_gemm calls, its LayerNorms wavlm_layernorm_fwd calls
+ * (unispeech_amd/transformer_lm.py).  Tensors WL_F32 or WL_BF16; accumulation, softmax state and results in fp32.
+ *   wavlm_lm_logprob      transformer.py:965-971 + get_normalized_probs(log_probs=True) + the target's entry, as FairseqLM reads
+ *                         it (examples/speech_recognition/w2l_decoder.py:366-383).  X [R, D] (row stride ldx), W [V, D] (row
+ *                         stride ldw; the output projection as the checkpoint stores it, no bias), target int32 [R]:
+ *                           z[r, v] = sum_i X[r, i] * W[v, i]   (fp32 accumulation; never stored)
+ *                           lse[r] = log sum_v exp z[r, v]      (optional: NULL = not wanted)
+ *                           logprob[r] = z[r, target[r]] - lse[r]
+ *                         target[r] < 0: a padding row, logprob[r] = 0.  target[r] >= V: logprob[r] = NaN (wavlm_ctc_loss treats
+ *                         bad labels the same way).  V is cut into slabs of 2048 entries -- a function of V alone; a workgroup
+ *                         owns 128 rows and one slab and keeps a running maximum, a running sum and the target's logit per row
+ *                         (online softmax; bf16 on v_mfma_f32_32x32x16_bf16 with the row on the lane, the target's logit taken
+ *                         from the same accumulator as the logits under the sum; fp32: fp32 FMA in k order).  Each (slab, row)
+ *                         writes (max, sum, target logit) to `workspace`; a second launch folds them in slab order.  No global
+ *                         atomics: bitwise reproducible, and a row's result depends neither on R nor on the row's position.
+ *                         workspace: wavlm_lm_logprob_workspace_bytes(R, V) = 12 bytes x R x ceil(V / 2048), rounded up to 256 --
+ *                         O(R x slabs), never O(R x V); 16-byte aligned.
+ *                         wavlm_lm_logprob_supported (host): 1 for D % 8 == 0, 8 <= D <= 8192, 1 <= V < 2^31 and the two dtypes.
+ *                         wavlm_lm_logprob returns -1 otherwise, and for a NULL pointer (lse excepted), ldx or ldw below D, X or W
+ *                         or a row stride that is not 16-byte aligned, a short workspace, or R x slabs beyond one grid dimension.
+ *   wavlm_attn_causal_fwd modules/transformer_layer.py:349-357 under the future mask (transformer.py:979-991): the packed qkv
+ *                         [B, T, 3 * H * d] and O [B, T, H * d] of wavlm_attn_plain_fwd; query t of sequence b attends keys 0..t.
+ *                         lengths int32 [B] on the device (NULL: every sequence is T long): rows t >= lengths[b] are written as
+ *                         zeros and no result reads them (right padding).  head_dim 32 or 64, any T >= 1, B * H <= 65535; online
+ *                         softmax, no [B H, T, T] tensor; key tiles entirely above the diagonal are skipped, not masked.  bf16:
+ *                         both products on v_mfma_f32_32x32x16_bf16 with fp32 softmax state; fp32: fp32 FMA throughout.  A
+ *                         sequence's result does not depend on B, on T beyond its length, or on its place in the batch.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_lm_logprob_supported(int32_t D, int32_t V, int32_t dtype);
+uint64_t wavlm_lm_logprob_workspace_bytes(int64_t R, int32_t V);
+int wavlm_lm_logprob(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t dtype, const int32_t* target, int64_t R,
+                     int32_t D, int32_t V, float* logprob, float* lse, void* workspace, uint64_t ws_bytes, void* stream);
+int wavlm_attn_causal_fwd_supported(int32_t head_dim, int32_t dtype);
+int wavlm_attn_causal_fwd(const void* qkv, void* O, const int32_t* lengths, int32_t B, int32_t H, int32_t T, int32_t head_dim,
+                          int32_t dtype, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

@@ -1,0 +1,132 @@
+"""Writes tests/golden/transformer_lm.npz: the reference's TransformerLanguageModel (fairseq.models.transformer
+TransformerDecoder(args, dictionary, embed, no_encoder_attn=True)) on the CPU, scored the way FairseqLM of
+examples/speech_recognition/w2l_decoder.py scores it: one sentence at a time, input [eos, w_1 .. w_n], log-softmax, the target's
+entry, -inf for unk.  Needs the reference checkout (oracle/ref_shim.py); run where it is, never on a test machine.
+
+No weights are stored: tests/transformer_lm_cases.py fill_state_dict refills either side's state dict from a seed.  Contents:
+  <M>/keys              the reference's state-dict names, M in A, B, C (tests/transformer_lm_cases.py MODELS)
+  <M>/logprobs, totals  fp32 [N, Tmax] target log-probs (0 behind a sentence's eos) and their sums, the reference in fp32
+  <M>/e_ref             the reference itself in bf16 on the CPU: max |bf16 - fp32| over the finite entries / max |fp32|
+  <M>/max               max |fp32| over the finite entries
+  rescore/order_<b>, s2_<b>   utterance b of the rescoring case: the hypotheses' indices in the first-pass n-best list, best first
+                        after rescoring with model A (unispeech_amd.ctc_lexicon.rescore_reference, float64), and their scores
+  rescore/tol           the rescoring tolerance the margin was checked against (every utterance: best - second > 2 tol)
+
+    python tools/gen_transformer_lm_golden.py
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import transformer_lm_cases as C  # noqa: E402
+
+HEAD_TOL = 5e-4                        # tests/test_diarization_gpu.py: the fp32-mode bound of a head, of the max magnitude
+
+
+def ref_args(opts):
+    from unispeech_amd.transformer_lm import TransformerLMConfig
+    a = argparse.Namespace(dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, relu_dropout=0.0, decoder_layerdrop=0.0,
+                           quant_noise_pq=0, quant_noise_pq_block_size=8, quant_noise_scalar=0, adaptive_softmax_cutoff=None,
+                           checkpoint_activations=False, offload_activations=False, export=False, tie_adaptive_proj=False,
+                           decoder_layers_to_keep=None, adaptive_softmax_dropout=0, adaptive_softmax_factor=4)
+    for k, v in TransformerLMConfig(opts).as_dict().items():
+        setattr(a, k, v)
+    return a
+
+
+def build_reference(name):
+    from fairseq.data import Dictionary
+    from fairseq.models.transformer import Embedding, TransformerDecoder
+    from fairseq.models.transformer_lm import TransformerLanguageModel
+    from fairseq.modules import AdaptiveInput
+    a = ref_args(C.MODELS[name])
+    d = Dictionary()
+    for i in range(C.VOCAB - 4):
+        d.add_symbol("word%d" % i)
+    assert len(d) == C.VOCAB and (d.pad(), d.eos(), d.unk()) == (C.PAD, C.EOS, C.UNK)
+    if a.adaptive_input:
+        embed = AdaptiveInput(len(d), d.pad(), a.decoder_input_dim, a.adaptive_input_factor, a.decoder_embed_dim,
+                              a.adaptive_input_cutoff, 0, 8)
+    else:
+        embed = Embedding(len(d), a.decoder_input_dim, d.pad())
+    model = TransformerLanguageModel(TransformerDecoder(a, d, embed, no_encoder_attn=True))
+    sd = model.state_dict()
+    filled = C.fill_state_dict(sd, C.SEEDS[name], a.share_decoder_input_output_embed)
+    # the buffers keep their own values: without `decoder.version` the reference takes the state dict for an old checkpoint and
+    # drops its final LayerNorm (upgrade_state_dict_named)
+    filled.update({k: v.clone() for k, v in sd.items() if k.rsplit(".", 1)[-1] in C.NOT_WEIGHTS})
+    model.load_state_dict(filled, strict=True)
+    assert (model.decoder.layer_norm is not None) == (a.decoder_normalize_before and not a.no_decoder_final_norm)
+    return model.eval(), sorted(sd)
+
+
+def score(model, sentences, dtype):
+    model = model.to(dtype)
+    Tmax = max(len(s) for s in sentences) + 1
+    out = np.zeros((len(sentences), Tmax), dtype=np.float32)
+    with torch.no_grad():
+        for i, s in enumerate(sentences):
+            res = model(torch.tensor([[C.EOS] + s]))
+            lp = model.get_normalized_probs(res, log_probs=True, sample=None)[0].float()
+            for t, w in enumerate(s + [C.EOS]):
+                out[i, t] = -math.inf if w == C.UNK else lp[t, w].item()
+    return out
+
+
+def main():
+    from oracle import ref_shim
+    ref_shim.install()
+    out, stats = {}, {}
+    for name in C.MODELS:
+        model, keys = build_reference(name)
+        lp = score(model, C.sentences(), torch.float32)
+        lb = score(model, C.sentences(), torch.bfloat16)
+        fin = np.isfinite(lp)
+        assert np.array_equal(fin, np.isfinite(lb))
+        mx = np.abs(lp[fin]).max()
+        e_ref = np.abs(lb[fin] - lp[fin]).max() / mx
+        out[name + "/keys"] = np.array(keys)
+        out[name + "/logprobs"] = lp
+        out[name + "/totals"] = lp.sum(1).astype(np.float32)
+        out[name + "/e_ref"] = np.float64(e_ref)
+        out[name + "/max"] = np.float64(mx)
+        stats[name] = (e_ref, mx)
+        print("model %s: max |log-prob| %.3f, bf16 reference on the CPU e_ref %.3e" % (name, mx, e_ref))
+
+    # rescoring: the float64 first pass, then the float64 second pass with model A; the margin between the two best s2 of every
+    # utterance must be more than twice the tolerance the GPU test grants, so that no utterance is excused from "same winner"
+    from unispeech_amd import ctc_lexicon as X
+    x, il, d, lexicon, opts, lm_dict = C.rescoring()
+    hyps = X.lexicon_beam_decode(x, il, d, lexicon, lexicon.lm, normalized=True, **opts)
+    lm = C.build("A")
+    res = X.rescore_reference(hyps, lm, lm_dict, lexicon.lm, opts["lm_weight"], opts["word_score"], **C.RESCORE_OPTS)
+    e_ref, mx = stats["A"]
+    tol_token = max(HEAD_TOL, 2 * e_ref) * mx
+    longest = max(len(h[0]) for utt in hyps for h in utt)
+    tol = C.RESCORE_OPTS["rescore_weight"] * (longest + 1) * tol_token
+    out["rescore/tol"] = np.float64(tol)
+    for b, (utt, r) in enumerate(zip(hyps, res)):
+        first = [(tuple(h[0]), tuple(h[1])) for h in utt]
+        order = [first.index((tuple(e["words"]), tuple(e["tokens"]))) for e in r]
+        s2 = np.array([e["score"] for e in r])
+        assert len(r) >= 2 and np.isfinite(s2[0]) and s2[0] - s2[1] > 2 * tol, (b, s2, tol)
+        print("utterance %d: %d hypotheses, order %s, s2 %s, margin %.4f > 2 x %.4f"
+              % (b, len(r), order, np.round(s2, 4), s2[0] - s2[1], tol))
+        out["rescore/order_%d" % b] = np.array(order, dtype=np.int64)
+        out["rescore/s2_%d" % b] = s2
+    path = os.path.join(ROOT, "tests", "golden", "transformer_lm.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 256 * 1024
+
+
+if __name__ == "__main__":
+    main()

@@ -11,6 +11,9 @@ HuBERT / WavLM / UniSpeech fine-tuning are produced.
   python -m unispeech_amd.ctc_lexicon decode CKPT DICT a.wav ... --lexicon FILE [--lm FILE.arpa]
   python -m unispeech_amd.ctc_lexicon score CKPT DICT MANIFEST.tsv LABELS.ltr --lexicon FILE [--lm FILE.arpa]
   with --beam --beam-size-token --beam-threshold --lm-weight --word-score --unk-weight --sil-weight --nbest
+  rescore_nbest / rescore_reference   second pass: the n-best list re-ranked with a Transformer LM (unispeech_amd.transformer_lm)
+  under the objective of the reference's W2lFairseqLMDecoder; --rescore-lm LM.pt --rescore-dict DICT.txt --rescore-weight W
+  --rescore-word-score S on the command line, together with --nbest N
 
 Tables (node 0 is the root; a node is a prefix of a spelling):
   child_off  int32 [N + 1]   node v's children are child_*[child_off[v] : child_off[v + 1]]
@@ -22,7 +25,8 @@ Tables (node 0 is the root; a node is a prefix of a spelling):
 The word LM is ctc_lm.NgramLM(order, entries, symbols=the lexicon's words): its tok_word maps a word id onto the LM's word, a
 word the LM does not list onto <unk>.
 
-Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm.  (Time
+Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm inside
+the first pass (it is the second pass above).  (Time
 steps: ctc_align.timesteps aligns a hypothesis's tokens.)  The criterion's wer_lexicon / wer_kenlm_model / wer_args stay refused (ctc.CtcCriterion).
 """
 import math
@@ -384,6 +388,67 @@ def lexicon_beam_decode(logits, input_lengths, dictionary, lexicon, lm=None, bea
               float(scores[b, h])) for h in range(int(n_hyp[b]))] for b in range(B)]
 
 
+# ------------------------------------------------------------------------------------------------------------ rescoring
+def ngram_sum(lm, words):
+    """S_ngram: what the first pass added for this word sequence before the LM weight -- sum of log10 p(w_i | history) from the
+    state of <s>, plus the sentence end -- in the search's own units.  words: strings, or the lexicon's word ids (the symbols the
+    NgramLM was built over); a word the LM does not list scores as its <unk>.  0 without a first-pass LM."""
+    if lm is None:
+        return 0.0
+    ids = lm.__dict__.get("_word_ids")
+    if ids is None:
+        ids = lm._word_ids = {w: i for i, w in enumerate(lm.words)}
+    st, total = lm.start, 0.0
+    for w in words:
+        wid = ids.get(w, ids[UNK]) if isinstance(w, str) else int(lm.tok_word[int(w)])
+        l, st = lm.score_word(st, wid)
+        total += l
+    return total + lm.score_eos(st)
+
+
+def _rescore(hyps, scorer, lm_dictionary, first_pass_lm, lm_weight, word_score, rescore_weight, rescore_word_score):
+    seqs, index = [], {}
+    for utt in hyps:
+        for h in utt:
+            key = tuple(int(lm_dictionary.index(w)) for w in h[0])      # by spelling; unknown to the LM -> its unk
+            if key not in index:
+                index[key] = len(seqs)
+                seqs.append(list(key))
+    totals = [float(v) for v in scorer(seqs)[1]] if seqs else []       # each distinct word sequence once
+    rw, out = float(rescore_weight), []
+    for utt in hyps:
+        res = []
+        for h in utt:
+            words, tokens, s1 = h[0], h[1], float(h[2])
+            tl = totals[index[tuple(int(lm_dictionary.index(w)) for w in words)]]
+            s2 = s1 - float(lm_weight) * ngram_sum(first_pass_lm, words) + (rw * tl if rw != 0.0 else 0.0) \
+                + (float(rescore_word_score) - float(word_score)) * len(words)
+            res.append({"words": list(words), "tokens": list(tokens), "score": s2, "lm_score": tl, "first_pass_score": s1})
+        out.append(sorted(res, key=lambda e: -e["score"]))              # stable: ties and all -inf keep first-pass order
+    return out
+
+
+def rescore_nbest(hyps, lm, lm_dictionary, first_pass_lm=None, lm_weight=0.0, word_score=0.0, rescore_weight=1.0,
+                  rescore_word_score=0.0):
+    """Second pass over the n-best lists of lexicon_beam_decode(..., nbest=N) with a transformer_lm.TransformerLM on the device:
+    every hypothesis's first-pass score s1 becomes
+        s2 = s1 - lm_weight * S_ngram(words) + rescore_weight * S_tlm(words) + (rescore_word_score - word_score) * len(words)
+    -- the objective of the reference's W2lFairseqLMDecoder (AM + lm_weight x LM + word_score x words + silence terms) evaluated on
+    that hypothesis, restricted to the list.  lm_weight / word_score: the first pass's options, first_pass_lm its NgramLM (None: it
+    had none); S_tlm: TransformerLM.score's total in natural log, as the reference feeds it to flashlight; words are mapped onto
+    lm_dictionary by spelling, one the LM does not know is its unk and scores -inf.  Returns, per utterance, the list re-sorted by
+    s2 (stable) as dicts with words, tokens, score, lm_score and first_pass_score."""
+    return _rescore(hyps, lm.score, lm_dictionary, first_pass_lm, lm_weight, word_score, rescore_weight, rescore_word_score)
+
+
+def rescore_reference(hyps, lm, lm_dictionary, first_pass_lm=None, lm_weight=0.0, word_score=0.0, rescore_weight=1.0,
+                      rescore_word_score=0.0):
+    """rescore_nbest in float64 over transformer_lm.score_reference: the specification"""
+    from .transformer_lm import score_reference
+    return _rescore(hyps, lambda s: score_reference(lm, s), lm_dictionary, first_pass_lm, lm_weight, word_score, rescore_weight,
+                    rescore_word_score)
+
+
 # ---------------------------------------------------------------------------------------------------------- command line
 def parse_args(argv=None):
     p, d, c = ctc.base_parser("python -m unispeech_amd.ctc_lexicon", __doc__.split("\n\n")[0],
@@ -394,7 +459,14 @@ def parse_args(argv=None):
         ctc.add_beam_options(q, "n-gram word LM (ARPA text) over the lexicon's words")
         q.add_argument("--word-score", type=float, default=1.0)
         q.add_argument("--unk-weight", type=float, default=-math.inf)
-    return ctc.refuse_binary_lm(p.parse_args(argv))
+        q.add_argument("--rescore-lm", default=None, metavar="LM.pt", help="Transformer LM checkpoint: re-rank the --nbest list")
+        q.add_argument("--rescore-dict", default=None, metavar="DICT.txt", help="the Transformer LM's fairseq dictionary")
+        q.add_argument("--rescore-weight", type=float, default=1.0)
+        q.add_argument("--rescore-word-score", type=float, default=None, help="default: --word-score")
+    a = ctc.refuse_binary_lm(p.parse_args(argv))
+    if (a.rescore_lm is None) != (a.rescore_dict is None):
+        p.error("--rescore-lm and --rescore-dict go together")
+    return a
 
 
 def _options(a):
@@ -406,13 +478,29 @@ def main(argv=None):
     d = ctc.LetterDictionary.load(a.dict)
     lexicon = Lexicon.load(a.lexicon, d, a.lm)
     kw = _options(a)
+    tlm = None
+    if a.rescore_lm is not None:
+        from .transformer_lm import TransformerLM
+        ld = ctc.LetterDictionary.load(a.rescore_dict)
+        tlm = TransformerLM.from_checkpoint(a.rescore_lm, len(ld), pad=ld.pad(), eos=ld.eos(), unk=ld.unk()).cuda()
+        if a.bf16:
+            tlm = tlm.to(torch.bfloat16)
+        rws = a.word_score if a.rescore_word_score is None else a.rescore_word_score
+
+    def search(logits, il, d):                  # the first pass, and the second if a Transformer LM was given
+        hyps = lexicon_beam_decode(logits, il, d, lexicon, lexicon.lm, **kw)
+        if tlm is None:
+            return hyps
+        res = rescore_nbest(hyps, tlm, ld, lexicon.lm, a.lm_weight if lexicon.lm is not None else 0.0, a.word_score,
+                            a.rescore_weight, rws)
+        return [[(e["words"], e["tokens"], e["score"]) for e in utt] for utt in res]
     if a.cmd == "score":
         def decoder(logits, il, d):
-            return [(h[0][1], h[0][0]) if h else ([], []) for h in lexicon_beam_decode(logits, il, d, lexicon, lexicon.lm, **kw)]
+            return [(h[0][1], h[0][0]) if h else ([], []) for h in search(logits, il, d)]
         return ctc.score(a, decoder)
 
     def lines(logits, d):                       # one line per hypothesis, best first; with --nbest above 1 the score in front
-        for words, _, sc in lexicon_beam_decode(logits, None, d, lexicon, lexicon.lm, **kw)[0]:
+        for words, _, sc in search(logits, None, d)[0]:
             text = " ".join(words)
             yield text if a.nbest == 1 else "%.4f\t%s" % (sc, text)
     return ctc.decode(a, lines)

@@ -48,12 +48,17 @@ def ptr(t, offset=0):
     return C.c_void_p(t.data_ptr() + offset * t.element_size())
 
 
+WS_MIN_BYTES = 10 << 20   # from here on torch's caching allocator gives a request a segment of its own size
+
+
 def workspace(device, nbytes, tag="main"):
-    """grow-only scratch buffer per (device, tag, stream): reuse is safe because the launches of one stream are ordered"""
+    """grow-only scratch buffer per (device, tag, stream): reuse is safe because the launches of one stream are ordered.
+    At least WS_MIN_BYTES: a long-lived 1 MiB buffer sits in the allocator's small pool and pins a 2 MiB segment whose other half
+    stays free for as long as the buffer lives -- a fragment every later small allocation of the process may be handed"""
     key = (device.index, tag, _RAW_STREAM(device.index) if _RAW_STREAM is not None else torch.cuda.current_stream(device).cuda_stream)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        buf = torch.empty(max(int(nbytes), WS_MIN_BYTES), dtype=torch.uint8, device=device)
         _WS[key] = buf
     return buf
 
@@ -965,6 +970,53 @@ def diar_estimate(z, S, E):
     check(_lib.lib().wavlm_diar_estimate(ptr(z), dt(z), z.stride(0), z.stride(1), B, T, int(S), int(E), ptr(act), ptr(vec), dt(vec),
                                          stream()), "wavlm_diar_estimate")
     return act, vec
+
+
+# ------------------------------------------------------------------------------------ Transformer LM
+def lm_logprob_supported(D, V, dtype):
+    return bool(_lib.lib().wavlm_lm_logprob_supported(int(D), int(V), BF16 if dtype == torch.bfloat16 else F32))
+
+
+def lm_logprob(x, w, target, want_lse=False):
+    """x [R, D] (unit channel stride), w [V, D], target int32 [R] -> (logprob fp32 [R], lse fp32 [R] or None):
+    logprob[r] = (w x_r)[target[r]] - logsumexp(w x_r), 0 for a negative target, NaN for one >= V.  The [R, V] logits never
+    exist: the workspace is 12 bytes per (row, slab of 2048 entries)."""
+    dev = _dev(x)
+    R, D = x.shape
+    V = w.shape[0]
+    if x.dtype != w.dtype or w.shape[1] != D or x.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError("x [R, D] and w [V, D] must share a dtype and D, with unit channel stride")
+    if target.dtype != torch.int32 or target.numel() != R or not target.is_contiguous():
+        raise ValueError("target must be a contiguous int32 tensor of %d entries" % R)
+    logprob = torch.empty(R, dtype=torch.float32, device=dev)
+    lse = torch.empty(R, dtype=torch.float32, device=dev) if want_lse else None
+    if R == 0:
+        return logprob, lse
+    L = _lib.lib()
+    need = L.wavlm_lm_logprob_workspace_bytes(R, V)
+    ws = workspace(dev, need, "lm_logprob")
+    check(L.wavlm_lm_logprob(ptr(x), x.stride(0), ptr(w), w.stride(0), dt(x), ptr(target), R, D, V, ptr(logprob), ptr(lse),
+                             ptr(ws), need, stream()), "wavlm_lm_logprob[R=%d D=%d V=%d]" % (R, D, V))
+    return logprob, lse
+
+
+def attn_causal_fwd(qkv, H, lengths=None, scale=None):
+    """packed qkv [B, T, 3 * H * d] (d = 32 or 64) -> causal softmax(scale * Q K^T) V as [B, T, H * d]; lengths int32 [B] on the
+    device (rows at or beyond a length come back as zeros); scale defaults to 1 / sqrt(d)"""
+    _dev(qkv)
+    _contig(qkv)
+    B, T, D3 = qkv.shape
+    d = D3 // (3 * H)
+    if d * 3 * H != D3:
+        raise ValueError("qkv width %d is not 3 * %d heads * head_dim" % (D3, H))
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous()
+                                or lengths.device != qkv.device):
+        raise ValueError("lengths must be a contiguous int32 tensor of %d entries on the device of qkv" % B)
+    O = torch.empty((B, T, H * d), dtype=qkv.dtype, device=qkv.device)
+    check(_lib.lib().wavlm_attn_causal_fwd(ptr(qkv), ptr(O), ptr(lengths), B, H, T, d, dt(qkv),
+                                           float(scale if scale is not None else d ** -0.5), stream()),
+          "wavlm_attn_causal_fwd[B=%d H=%d T=%d d=%d]" % (B, H, T, d))
+    return O
 
 
 # ---------------------------------------------------------------------------------------------- CTC
