@@ -1,4 +1,6 @@
-"""CTC fine-tuning, host side (unispeech_amd/ctc.py): the float64 restatement against torch's F.ctc_loss, the criterion against a
+"""CTC fine-tuning, host side (unispeech_amd/ctc.py): the float64 restatement against torch's F.ctc_loss (another blank than 0
+included), the conditions that the cases of tests/ctc_cases.py must meet for the GPU parity tests to mean something (every
+kernel variant reached; the tolerance neither blind nor below the output format), the criterion against a
 restatement of the reference's criterions/ctc.py:110-160 on a stub model, the edit distance, the greedy decode's host path, the
 key set and the refusals of EncoderCtc, and the ABI bookkeeping.  No GPU."""
 import os
@@ -40,6 +42,80 @@ def test_reference_equals_torch_float64(name):
         padded[b, :tl[b]] = targets.numpy()[offs[b]:offs[b + 1]]
     pl, _ = ctc_reference(logits.double().numpy(), padded, il, tl, CC.BLANK)
     assert np.array_equal(pl, loss)
+
+
+@pytest.mark.parametrize("name", list(CC.BLANK_CASES))
+def test_reference_equals_torch_float64_with_another_blank(name):
+    """blank = C - 1, and blank = 7 with labels that are 7 themselves"""
+    from unispeech_amd.ctc import ctc_reference
+    logits, targets, il, tl = CC.case(name)
+    blank = CC.BLANK_CASES[name]["blank"]
+    first = targets[:tl[0]].tolist()
+    assert blank != CC.BLANK and (blank in first) == (name == "blank7")
+    if name == "blank7":
+        assert first[2] == first[3] == first[10] == 7 and first.count(7) == 3
+    l64, g64 = CC.ref64(name, blank=blank)
+    assert np.isfinite(l64).all() and CC.INF_SAMPLES[name] == []
+    loss, grad = ctc_reference(logits.double().numpy(), targets.numpy(), il, tl, blank)
+    assert (np.abs(loss - l64) <= 1e-10 * np.abs(l64)).all() and np.abs(grad - g64).max() <= 1e-10 * np.abs(g64).max()
+    wrong, _ = CC.ref64(name)                            # the blank matters: with blank 0 the same labels cost something else
+    assert (np.abs(wrong - l64) > 1e-3 * l64).all()
+
+
+def test_the_new_cases_reach_every_variant_and_their_bound_can_tell():
+    """Conditions on the inputs of tests/ctc_cases.py, decided by the references alone (torch float64 and torch fp32 on the
+    CPU), on the fp32 logits and on their bf16 roundings.
+    Coverage: the cases reach PER = 1, 2, 4, 8, each with a sample shorter than the batch's longest, and S on both sides of every
+    boundary.  Peaked cases: 4 x E32 is at most 1 % of the sample's largest gradient and 1e-4 of its loss, so an error of a few
+    per cent cannot pass.  Every new case: E32 is at least 2^-24 of the loss and of the largest gradient -- half an ulp of an fp32
+    output at most, so the float64 result rounded to fp32 is within the bound.  The random cases are exempt from the 1 % cap
+    (their ratio is printed)."""
+    reached, with_rider, S_seen = set(), set(), set()
+    for name, c in list(CC.CASES.items()) + list(CC.BLANK_CASES.items()):
+        per = CC.variant(max(c["tl"]))
+        reached.add(per)
+        S_seen.add(2 * max(c["tl"]) + 1)
+        if min(c["tl"]) < max(c["tl"]):
+            with_rider.add(per)
+        if name in CC.NEW_CASES and name in CC.CASES:
+            assert name.endswith("_per%d" % per), "the name of a case states the variant it runs"
+    assert reached == with_rider == {1, 2, 4, 8}
+    assert {255, 257, 511, 513, 1023, 1025, 2047} <= S_seen
+    assert [c["tl"] for c in CC.CASES.values()].count([1023, 0, 5, 300]) == 1       # the riders that are also run alone
+    assert CC.variant(5) == 1 and CC.variant(300) == 4 and CC.variant(1023) == 8
+    for name in CC.NEW_CASES:
+        c = CC.CASES[name] if name in CC.CASES else CC.BLANK_CASES[name]
+        blank = c.get("blank", CC.BLANK)
+        for bf16 in (False, True):
+            l64, g64 = CC.ref64(name, False, bf16, blank)
+            el, eg = CC.e32(name, bf16, blank)
+            assert [b for b in range(c["B"]) if not np.isfinite(l64[b])] == CC.INF_SAMPLES[name]
+            zl, zg = CC.ref64(name, True, bf16, blank)
+            for b in range(c["B"]):
+                if b in CC.INF_SAMPLES[name]:
+                    assert c["il"][b] < c["T"] and zl[b] == 0 and (zg[:, b] == 0).all()
+                    continue
+                gmax = np.abs(g64[:, b]).max()
+                print("ctc conditions %s %s sample %d: loss %.6g, 4 E32loss / loss %.2e, E32loss / (2^-24 loss) %.2f; max |g| %.3f, "
+                      "4 E32grad / max |g| %.2e" % (name, "bf16" if bf16 else "fp32", b, l64[b], 4 * el[b] / max(l64[b], 1e-300),
+                                                   el[b] / max(2.0 ** -24 * l64[b], 1e-300), gmax, 4 * eg[b] / max(gmax, 1e-300)))
+                assert el[b] >= 2.0 ** -24 * l64[b] and eg[b] >= 2.0 ** -24 * gmax
+                if "peak" in c:
+                    assert 4 * eg[b] <= 0.01 * gmax and 4 * el[b] <= 1e-4 * l64[b]
+    for name, c in CC.CASES.items():
+        if "peak" in c:
+            assert c["C"] == 32 and min(c["il"]) < c["T"]
+            _, targets, _, tl = CC.case(name)
+            if "labels" not in c:
+                assert targets[1] == targets[0] and targets[3] == targets[2]
+    # the label structures the table promises
+    _, t, _, tl = CC.case("runs256_per4")
+    same, alt = t[:256], t[256:]
+    assert (same == same[0]).all() and (alt[::2] == alt[0]).all() and (alt[1::2] == alt[1]).all() and alt[0] != alt[1]
+    _, t, _, tl = CC.case("C1024_per1")
+    assert {768, 1023} <= set(t[:tl[0]].tolist()) and 1023 in t[tl[0]:].tolist()
+    _, t, _, tl = CC.case("C257_per1")
+    assert 256 in t[:tl[0]].tolist() and 256 in t[tl[0]:].tolist()
 
 
 def test_reference_input_length_zero_and_host_autograd():

@@ -7,11 +7,25 @@ kernel must lie within 4 x E32 of the float64 value (the factor of the fp32 fron
 chain of several hundred steps rounds differently in any other evaluation order.  bf16 logits: float64 on the bf16 values, the
 same loss bound; for the gradient, its one rounding to bf16 is added to 4 x E32.  bf16 keeps 8 significant bits, so rounding to
 nearest moves a value g by up to 2^-8 |g| (just above a power of two) and no bf16 output can do better: the bound is, element by
-element, err[t, c] <= 4 x E32 + 2^-8 |g[t, c]|.  The issue wrote 2^-9 |g|; that holds per sample with |g| the sample's largest
-magnitude and is asserted in that form as well, but element by element it is below the format's own rounding: the test prints
-the largest (err - 4 x E32) / |g| in units of 2^-9 (measured: up to 1.84, i.e. between 2^-9 and 2^-8).  Worst ratios are printed
+element, err[t, c] <= 4 x E32 + 2^-8 |g[t, c]|.  The issue wrote 2^-9 |g|; element by element that is below the format's own
+rounding: the test prints the largest (err - 4 x E32) / |g| in units of 2^-9 (measured: up to 1.84, i.e. between 2^-9 and 2^-8).
+Per sample it is asserted as well, as 4 x E32 + 2^-9 P with P the power of two at or above the sample's largest |g|: half a bf16
+ulp of the largest elements.  (It used to read 2^-9 max |g|, which cases A to E meet only because their largest |g| is 0.92 to
+1.00; in the peaked cases it is 0.51 to 0.87, an element between 0.5 and that rounds by up to 2^-9 whatever computed it, and the
+kernel's correctly rounded output measured 0.00194 against 0.00189.)  Worst ratios are printed
 (-s); for bf16 the printed gradient ratio is the largest (err - 2^-8 |g|) / E32 over the elements, floored at 0.
-A sample without an alignment: loss inf and, as in torch, NaN in its gradient rows; under zero_infinity exactly 0 for both."""
+A sample without an alignment: loss inf and, as in torch, NaN in its gradient rows; under zero_infinity exactly 0 for both.
+
+Variants.  The two heavy kernels are compiled for 1, 2, 4 or 8 extended positions per lane (S = 2 Lmax + 1 up to 256, 512, 1024,
+2047) and the longest target of a batch picks the variant for all of it.  The parity tests run every case of ctc_cases.CASES in
+both dtypes; the names of the cases added for this carry the variant (L127_per1 ... L1023_per8: S = 255 | 257, 511 | 513,
+1023 | 1025 and 2047), and tests/test_ctc.py asserts without a GPU that together they reach all four, that each variant meets a
+sample shorter than the batch's longest, and that 4 x E32 of the peaked cases is below 1 % of the gradient.  Across variants
+(test_same_bits_in_every_variant): the L = 5 and L = 300 samples of the Lmax = 1023 batch run alone (PER 1 and PER 4), the
+two together (L = 5 under PER 4), the L = 0 sample alone, and the L = 90 sample of L128_per2 alone (PER 1 beside PER 2) give
+torch.equal loss and gradient rows to what they give in their batch, in fp32 and bf16; so do a permutation of the Lmax = 1023
+batch and a second run of it.  Another blank than 0, and labels that name the blank (ctc_cases.BLANK_CASES), go through the same
+parity check; strides, the guard band and autograd are repeated on a PER = 4 case."""
 import numpy as np
 import pytest
 import torch
@@ -43,7 +57,7 @@ def _args(targets, tl, il):
     return t, off, int(sum(tl)), int(max(tl)), torch.tensor(il, dtype=torch.int32).cuda()
 
 
-def _run(name, dtype=torch.float32, zero_infinity=False, tbc_view=False, samples=None, grad_out=None):
+def _run(name, dtype=torch.float32, zero_infinity=False, tbc_view=False, samples=None, grad_out=None, blank=CC.BLANK):
     """(nll [B], dlogits [T, B, C]) as float64 numpy + the raw device tensors; samples: a subset / permutation of the batch"""
     from unispeech_amd import ops
     logits, targets, il, tl = CC.case(name)
@@ -56,7 +70,7 @@ def _run(name, dtype=torch.float32, zero_infinity=False, tbc_view=False, samples
         x = x.contiguous().cuda().transpose(0, 1)              # T x B x C storage, read through its [B, T, C] view
     else:
         x = x.transpose(0, 1).contiguous().cuda()              # batch-first storage
-    nll, dx = ops.ctc_loss_fwd_bwd(x, *_args(targets, tl, il), CC.BLANK, grad_out, zero_infinity)
+    nll, dx = ops.ctc_loss_fwd_bwd(x, *_args(targets, tl, il), blank, grad_out, zero_infinity)
     torch.cuda.synchronize()
     return nll, dx.transpose(0, 1)
 
@@ -65,12 +79,12 @@ def f64(t):
     return t.detach().float().cpu().numpy().astype(np.float64)
 
 
-def _check_parity(name, dtype):
+def _check_parity(name, dtype, blank=CC.BLANK):
     bf16 = dtype == torch.bfloat16
     _, _, il, tl = CC.case(name)
-    l64, g64 = CC.ref64(name, False, bf16)
-    el, eg = CC.e32(name, bf16)
-    nll_t, dx_t = _run(name, dtype)
+    l64, g64 = CC.ref64(name, False, bf16, blank)
+    el, eg = CC.e32(name, bf16, blank)
+    nll_t, dx_t = _run(name, dtype, blank=blank)
     nll, dx = f64(nll_t), f64(dx_t)
     assert dx_t.dtype == dtype and nll_t.dtype == torch.float32
     inf = CC.INF_SAMPLES[name]
@@ -85,9 +99,10 @@ def _check_parity(name, dtype):
         err_g = np.abs(dx[:, b] - g64[:, b])
         slack = 2.0 ** -8 * np.abs(g64[:, b]) if bf16 else 0.0                 # element by element: the rounding to bf16
         rl = err_l / el[b] if el[b] > 0 else (0.0 if err_l == 0 else np.inf)
-        rg = max(float((err_g - slack).max() / eg[b]), 0.0)
-        if bf16:
-            big = np.abs(g64[:, b]) > 1e-3
+        over = float((err_g - slack).max())
+        rg = max(over / eg[b], 0.0) if eg[b] > 0 else (0.0 if over <= 0 else np.inf)     # E32 = 0: a single class, all zeros
+        big = np.abs(g64[:, b]) > 1e-3
+        if bf16 and big.any():
             print("ctc parity %s bf16 sample %d: largest (err - 4 E32) / |g| = %.3f x 2^-9 over the elements with |g| > 1e-3"
                   % (name, b, float(((err_g[big] - 4 * eg[b]) / np.abs(g64[:, b][big])).max() * 2.0 ** 9)))
         print("ctc parity %s %s sample %d: loss %.6g err %.3e (E32 %.3e, ratio %.3f); grad err %.3e (E32 %.3e, ratio %.3f)"
@@ -95,11 +110,12 @@ def _check_parity(name, dtype):
         worst_l, worst_g = max(worst_l, rl), max(worst_g, rg)
         assert err_l <= 4 * el[b]
         assert (err_g <= 4 * eg[b] + slack).all()
-        if bf16:
-            assert err_g.max() <= 4 * eg[b] + 2.0 ** -9 * np.abs(g64[:, b]).max()   # the issue's form, per sample like E32
+        gmax = np.abs(g64[:, b]).max()
+        if bf16 and gmax > 0:                                   # per sample like E32: half a bf16 ulp at the largest magnitude
+            assert err_g.max() <= 4 * eg[b] + 2.0 ** -9 * 2.0 ** np.ceil(np.log2(gmax))
     print("ctc parity %s %s: worst loss ratio %.3f, worst gradient ratio %.3f" % (name, "bf16" if bf16 else "fp32", worst_l, worst_g))
     # zero_infinity: the samples without an alignment are exactly zero, the others the same bits
-    z_nll, z_dx = _run(name, dtype, zero_infinity=True)
+    z_nll, z_dx = _run(name, dtype, zero_infinity=True, blank=blank)
     for b in range(len(il)):
         if b in inf:
             assert z_nll[b].item() == 0.0 and (z_dx[:, b] == 0).all()
@@ -117,13 +133,21 @@ def test_parity_bf16(name):
     _check_parity(name, torch.bfloat16)
 
 
-def test_strides_and_guard_band():
+@pytest.mark.parametrize("name", list(CC.BLANK_CASES))
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_parity_with_another_blank(name, dtype):
+    """blank = C - 1; blank = 7 with three labels that are 7 themselves (two of them a repeated pair): the blank wave owns those
+    positions, and the ranks of the other classes skip over them"""
+    _check_parity(name, dtype, CC.BLANK_CASES[name]["blank"])
+
+
+def _check_strides_and_guard_band(name):
     from unispeech_amd import ops
-    a_nll, a_dx = _run("B")
-    b_nll, b_dx = _run("B", tbc_view=True)
+    a_nll, a_dx = _run(name)
+    b_nll, b_dx = _run(name, tbc_view=True)
     assert torch.equal(a_nll, b_nll) and torch.equal(a_dx, b_dx)
     # a view of a wider buffer: [B, T + 3, C + 5] storage, frames 2 .. T + 1 and classes 0 .. C - 1 of it
-    logits, targets, il, tl = CC.case("B")
+    logits, targets, il, tl = CC.case(name)
     T, B, C = logits.shape
     wide_x = torch.full((B, T + 3, C + 5), 123.0, device="cuda")
     wide_x[:, 2:T + 2, :C] = logits.transpose(0, 1).cuda()
@@ -137,6 +161,16 @@ def test_strides_and_guard_band():
     assert (wide_g[outside] == 7.0).all(), "bytes outside the B x T x C view were written"
 
 
+def test_strides_and_guard_band():
+    _check_strides_and_guard_band("B")
+
+
+def test_strides_and_guard_band_at_four_positions_per_lane():
+    """S = 1023: the alpha workspace's stride and the dx stores of the second to fourth sweep"""
+    assert CC.variant(max(CC.case("L511_per4")[3])) == 4
+    _check_strides_and_guard_band("L511_per4")
+
+
 def test_reproducible_and_independent_of_the_batch():
     a = _run("E")
     b = _run("E")
@@ -148,6 +182,35 @@ def test_reproducible_and_independent_of_the_batch():
     p_nll, p_dx = _run("E", samples=perm)
     for i, b in enumerate(perm):
         assert torch.equal(p_nll[i], a[0][b]) and torch.equal(p_dx[:, i], a[1][:, b])
+
+
+def _same_bits(name, dtype, samples, batch):
+    """the samples run as a batch of their own give the bits of their rows in `batch`, the (nll, dx) of the whole case"""
+    nll, dx = _run(name, dtype, samples=samples)
+    for i, b in enumerate(samples):
+        assert torch.equal(nll[i], batch[0][b]), (name, samples, b)
+        assert torch.equal(dx[:, i], batch[1][:, b]), (name, samples, b)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_same_bits_in_every_variant(dtype):
+    """a sample's loss and gradient do not depend on the variant its batch picks: the riders of the Lmax = 1023 batch (PER 8,
+    alpha stride 2047) alone, where the L = 5 one runs PER 1 with stride 11 and the L = 300 one PER 4 with stride 601"""
+    name = "L1023_per8"
+    tl = CC.case(name)[3]
+    assert tl == [1023, 0, 5, 300] and [CC.variant(L) for L in tl] == [8, 1, 1, 4]
+    batch = _run(name, dtype)
+    again = _run(name, dtype)
+    assert torch.equal(batch[0], again[0]) and torch.equal(batch[1], again[1])
+    assert torch.isfinite(batch[0]).all() and (batch[0] > 0).all()
+    _same_bits(name, dtype, [2], batch)              # PER 1
+    _same_bits(name, dtype, [3], batch)              # PER 4
+    _same_bits(name, dtype, [1], batch)              # the empty target: S = 1
+    _same_bits(name, dtype, [2, 3], batch)           # L = 5 under PER 4
+    _same_bits(name, dtype, [3, 1, 0, 2], batch)     # a permutation of the batch
+    name = "L128_per2"
+    assert [CC.variant(L) for L in CC.case(name)[3]] == [2, 1]
+    _same_bits(name, dtype, [1], _run(name, dtype))  # PER 1 alone, PER 2 in its batch
 
 
 def test_edge_inputs_against_the_restatement():
@@ -184,7 +247,7 @@ def test_edge_inputs_against_the_restatement():
     assert torch.isnan(nll[3]) and (dx[3] == 0).all() and torch.equal(nll[:2], good_nll[:2])
 
 
-@pytest.mark.parametrize("name", ["B", "C"])
+@pytest.mark.parametrize("name", ["B", "C", "L511_per4"])
 def test_autograd(name):
     from unispeech_amd.ctc import ctc_loss
     logits, targets, il, tl = CC.case(name)
