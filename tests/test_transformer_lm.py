@@ -245,3 +245,71 @@ def test_rescoring_case_of_the_fixture(g):
 
 def test_fixture_is_small():
     assert os.path.getsize(os.path.join(GOLDEN, "transformer_lm.npz")) < 256 * 1024
+    assert os.path.getsize(os.path.join(GOLDEN, "transformer_lm_wide.npz")) < 256 * 1024
+
+
+# ------------------------------------------------------------------------------------------- the models at production width
+@pytest.mark.parametrize("name", list(C.WIDE_MODELS))
+def test_wide_score_reference_equals_the_fixture(name):
+    """models W and X (D 512 / 256, V 5003, sentences of up to 200 words) against tests/golden/transformer_lm_wide.npz: the bound
+    of test_score_reference_equals_the_fixture"""
+    from unispeech_amd.transformer_lm import score_reference
+    g = load_golden("transformer_lm_wide.npz")
+    s = C.wide_sentences()
+    assert [len(x) for x in s] == [0, 1, 126, 127, 128, 200] and C.WIDE_VOCAB > 2 * C.LM_SLAB and C.WIDE_VOCAB % C.LM_TILE
+    lp, tot = (v.numpy() for v in score_reference(C.build_wide(name), s))
+    want = g[name + "/logprobs"]
+    assert lp.shape == want.shape == (6, 201)
+    fin = np.isfinite(want)
+    assert np.array_equal(fin, np.isfinite(lp))
+    err = np.abs(lp[fin] - want[fin]).max()
+    print(name, "max |score_reference - reference| = %.3e" % err)
+    assert err <= 1e-5
+    i, t = C.WIDE_UNK_AT
+    assert s[i][t] == C.UNK and lp[i, t] == -math.inf and tot[i] == -math.inf and (~fin).sum() == 1
+    for i in range(6):
+        if i != C.WIDE_UNK_AT[0]:
+            assert abs(tot[i] - float(g[name + "/totals"][i])) <= 1e-5 * (len(s[i]) + 1) + 1e-5
+        assert not lp[i, len(s[i]) + 1:].any()
+    assert float(g[name + "/max"]) == np.abs(want[fin]).max() and 0 < float(g[name + "/e_ref"]) < 0.05
+
+
+# ------------------------------------------------------------- what the built kernel cases of the GPU suite rest on
+def test_slot_targets_cover_every_position_of_a_tile():
+    """each block of 128 rows has a target at each of the 128 positions of a tile; the first block's tile is the last one of slab
+    0, the second block's targets lie in slab 1 as far as it has entries"""
+    t = C.slot_targets().numpy()
+    assert t.shape == (256,) and t.min() >= 0 and t.max() < 2051
+    for b in range(2):
+        assert sorted(t[128 * b:128 * b + 128] % C.LM_TILE) == list(range(128))
+    assert (t[:128] // C.LM_TILE == 15).all() and (t[:128] // C.LM_SLAB == 0).all()
+    assert t[128:131].tolist() == [2048, 2049, 2050] and (t[131:] // C.LM_TILE == 14).all()
+    assert np.array_equal(C.slot_case()[2].numpy(), t)
+
+
+def test_staircase_keeps_the_online_softmax_rescaling():
+    """from the float64 logits alone: the c = 2 row renews its running tile maximum in at least 40 of the 49 tiles while no tile
+    holds more than 40 % of its mass, and in the c = 0 row each of the three full slabs holds 25 % to 40 %"""
+    X, W, tgt, z, lse, lp = C.staircase_case()
+    assert torch.equal(X, C.bf16_valued(X)) and torch.equal(W, C.bf16_valued(W))
+    assert X[:, 0].tolist() == list(C.STAIR_C) and z.shape == (5, 6200)
+    tiles, renew, share, slabs = C.staircase_profile(z[0])
+    print("c = 2: %d of %d tiles renew the maximum, largest tile %.2f, slabs %s" % (renew, tiles, share, np.round(slabs, 2)))
+    assert tiles == 49 and renew >= 40 and share <= 0.40
+    tiles, renew, share, slabs = C.staircase_profile(z[4])
+    print("c = 0: slabs", np.round(slabs, 3))
+    assert len(slabs) == 4 and all(0.25 <= s <= 0.40 for s in slabs[:3])
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_rising_scores_keep_the_attention_rescaling(d):
+    """from the float64 scores alone, for queries >= 128 of the rising heads: at least three quarters of the 32-key steps a query
+    sees renew its running maximum and no step holds more than half of its mass"""
+    qkv = C.rising_causal_qkv(d)
+    assert torch.equal(qkv, C.bf16_valued(qkv))
+    x = qkv.view(C.RISING_B, C.RISING_T, 3, C.RISING_H, d)
+    assert (x[:, :, 0, 0, 0] == C.rising_constant(d)).all() and (x[:, :, 0, 1, 0] == -C.rising_constant(d)).all()
+    assert torch.equal(x[0, :, 1, 3, 0], (torch.arange(C.RISING_T) // 32).float() / 4)
+    renew, share = C.rising_profile(qkv, d)
+    print("d %d: smallest fraction of renewing steps %.2f, largest share of one step %.2f" % (d, renew, share))
+    assert renew >= 0.75 and share <= 0.5

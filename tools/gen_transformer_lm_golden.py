@@ -12,7 +12,10 @@ No weights are stored: tests/transformer_lm_cases.py fill_state_dict refills eit
                         after rescoring with model A (unispeech_amd.ctc_lexicon.rescore_reference, float64), and their scores
   rescore/tol           the rescoring tolerance the margin was checked against (every utterance: best - second > 2 tol)
 
-    python tools/gen_transformer_lm_golden.py
+--wide writes tests/golden/transformer_lm_wide.npz instead: models W and X (WIDE_MODELS: D 512 and 256, V 5003) on sentences of up
+to 200 words, <M>/logprobs, totals, e_ref and max by the same recipe.
+
+    python tools/gen_transformer_lm_golden.py [--wide]
 """
 import argparse
 import math
@@ -42,16 +45,17 @@ def ref_args(opts):
     return a
 
 
-def build_reference(name):
+def build_reference(name, models=None, vocab=None, seeds=None):
+    models, vocab, seeds = models or C.MODELS, vocab or C.VOCAB, seeds or C.SEEDS
     from fairseq.data import Dictionary
     from fairseq.models.transformer import Embedding, TransformerDecoder
     from fairseq.models.transformer_lm import TransformerLanguageModel
     from fairseq.modules import AdaptiveInput
-    a = ref_args(C.MODELS[name])
+    a = ref_args(models[name])
     d = Dictionary()
-    for i in range(C.VOCAB - 4):
+    for i in range(vocab - 4):
         d.add_symbol("word%d" % i)
-    assert len(d) == C.VOCAB and (d.pad(), d.eos(), d.unk()) == (C.PAD, C.EOS, C.UNK)
+    assert len(d) == vocab and (d.pad(), d.eos(), d.unk()) == (C.PAD, C.EOS, C.UNK)
     if a.adaptive_input:
         embed = AdaptiveInput(len(d), d.pad(), a.decoder_input_dim, a.adaptive_input_factor, a.decoder_embed_dim,
                               a.adaptive_input_cutoff, 0, 8)
@@ -59,7 +63,7 @@ def build_reference(name):
         embed = Embedding(len(d), a.decoder_input_dim, d.pad())
     model = TransformerLanguageModel(TransformerDecoder(a, d, embed, no_encoder_attn=True))
     sd = model.state_dict()
-    filled = C.fill_state_dict(sd, C.SEEDS[name], a.share_decoder_input_output_embed)
+    filled = C.fill_state_dict(sd, seeds[name], a.share_decoder_input_output_embed)
     # the buffers keep their own values: without `decoder.version` the reference takes the state dict for an old checkpoint and
     # drops its final LayerNorm (upgrade_state_dict_named)
     filled.update({k: v.clone() for k, v in sd.items() if k.rsplit(".", 1)[-1] in C.NOT_WEIGHTS})
@@ -81,25 +85,45 @@ def score(model, sentences, dtype):
     return out
 
 
+def score_both(model, sentences, name, out):
+    """the reference in fp32 and in bf16 on the CPU: <name>/logprobs, totals, e_ref, max into `out`; -> (e_ref, max)"""
+    lp = score(model, sentences, torch.float32)
+    lb = score(model, sentences, torch.bfloat16)
+    fin = np.isfinite(lp)
+    assert np.array_equal(fin, np.isfinite(lb))
+    mx = np.abs(lp[fin]).max()
+    e_ref = np.abs(lb[fin] - lp[fin]).max() / mx
+    out[name + "/logprobs"] = lp
+    out[name + "/totals"] = lp.sum(1).astype(np.float32)
+    out[name + "/e_ref"] = np.float64(e_ref)
+    out[name + "/max"] = np.float64(mx)
+    print("model %s: max |log-prob| %.3f, bf16 reference on the CPU e_ref %.3e" % (name, mx, e_ref))
+    return e_ref, mx
+
+
+def main_wide():
+    """tests/golden/transformer_lm_wide.npz: models W and X of tests/transformer_lm_cases.py WIDE_MODELS on wide_sentences(), the
+    same recipe; <M>/logprobs, totals, e_ref, max only"""
+    from oracle import ref_shim
+    ref_shim.install()
+    out = {}
+    for name in C.WIDE_MODELS:
+        model, _ = build_reference(name, C.WIDE_MODELS, C.WIDE_VOCAB, C.WIDE_SEEDS)
+        score_both(model, C.wide_sentences(), name, out)
+    path = os.path.join(ROOT, "tests", "golden", "transformer_lm_wide.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 256 * 1024
+
+
 def main():
     from oracle import ref_shim
     ref_shim.install()
     out, stats = {}, {}
     for name in C.MODELS:
         model, keys = build_reference(name)
-        lp = score(model, C.sentences(), torch.float32)
-        lb = score(model, C.sentences(), torch.bfloat16)
-        fin = np.isfinite(lp)
-        assert np.array_equal(fin, np.isfinite(lb))
-        mx = np.abs(lp[fin]).max()
-        e_ref = np.abs(lb[fin] - lp[fin]).max() / mx
         out[name + "/keys"] = np.array(keys)
-        out[name + "/logprobs"] = lp
-        out[name + "/totals"] = lp.sum(1).astype(np.float32)
-        out[name + "/e_ref"] = np.float64(e_ref)
-        out[name + "/max"] = np.float64(mx)
-        stats[name] = (e_ref, mx)
-        print("model %s: max |log-prob| %.3f, bf16 reference on the CPU e_ref %.3e" % (name, mx, e_ref))
+        stats[name] = score_both(model, C.sentences(), name, out)
 
     # rescoring: the float64 first pass, then the float64 second pass with model A; the margin between the two best s2 of every
     # utterance must be more than twice the tolerance the GPU test grants, so that no utterance is excused from "same winner"
@@ -129,4 +153,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--wide", action="store_true", help="write tests/golden/transformer_lm_wide.npz (models W and X) instead")
+    main_wide() if p.parse_args().wide else main()
