@@ -924,6 +924,35 @@ int wavlm_attn_causal_fwd(const void* qkv, void* O, const int32_t* lengths, int3
                           int32_t dtype, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Transformer LM, incremental decoding (csrc/lm_step.hip; additive to ABI 30: two new symbols, nothing else changes).
+ *   wavlm_attn_step       single-query self-attention over a tree-shaped KV cache: one new token per row, the rows' prefixes
+ *                         forming a tree (the word histories of a beam).  A cache entry ("slot") holds the K and the V of one
+ *                         token of one layer: Kc, Vc [slots, H * d] (row stride ld_kv).  Row r brings its packed q | k | v
+ *                         (qkv [R, 3 * H * d], row stride ld_qkv); slot[r] names the slot its own k and v are written to;
+ *                         anc[r * ld_anc + 0 .. lengths[r] - 2] (int32) names the slots of its ancestors in position order;
+ *                         lengths[r] counts the row itself.
+ *                           O[r, h * d + :] = softmax(scale * q[r, h] . [K[anc[r, .], h] ; k[r, h]]) [V[anc[r, .], h] ; v[r, h]]
+ *                         fp32 softmax state and accumulation, online softmax, no score tensor.  The own k and v are stored
+ *                         from the registers the softmax uses, by the same launch; a row never reads a slot written in that
+ *                         launch (the caller evaluates parents before children and names each slot once per launch).
+ *                         lengths[r] <= 0: O[r] is zeros and nothing is stored.  Entries of anc at or beyond lengths[r] - 1
+ *                         are never read; slots not named are never read.  What a caller must not pass is answered without
+ *                         forming an address: lengths[r] > max_length, slot[r] outside [0, slots) or a read ancestor outside
+ *                         [0, slots) gives a row of NaN and stores nothing.  One wave per (row, head), the 64 lane states
+ *                         folded in lane order: no atomics, bitwise reproducible, a row's bits depend neither on R nor on its
+ *                         place in the batch.  head_dim 32 or 64, WL_F32 or WL_BF16.
+ *                         Returns -1 before any launch for a NULL pointer, qkv / Kc / Vc / O or a row stride of theirs that is
+ *                         not 16-byte aligned, an int32 array that is not 4-byte aligned, two of qkv / Kc / Vc / O whose
+ *                         byte ranges (first row to the end of the last) overlap, a row stride shorter than its row,
+ *                         ld_anc < max_length - 1, an unsupported head width or dtype, R, H, slots or max_length below 1, or
+ *                         R * H beyond one grid dimension.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_attn_step_supported(int32_t head_dim, int32_t dtype);
+int wavlm_attn_step(const void* qkv, int64_t ld_qkv, void* Kc, void* Vc, int64_t ld_kv, int64_t slots, const int32_t* slot,
+                    const int32_t* anc, int64_t ld_anc, const int32_t* lengths, int32_t max_length, void* O, int64_t ld_o,
+                    int32_t R, int32_t H, int32_t head_dim, int32_t dtype, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

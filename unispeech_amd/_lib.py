@@ -245,6 +245,9 @@ SIGNATURES = {
     "wavlm_lm_logprob": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_u64, c_vp]),
     "wavlm_attn_causal_fwd_supported": (c_i32, [c_i32, c_i32]),
     "wavlm_attn_causal_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "wavlm_attn_step_supported": (c_i32, [c_i32, c_i32]),
+    "wavlm_attn_step": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32,
+                                c_i32, c_i32, c_f32, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

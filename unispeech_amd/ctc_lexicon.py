@@ -14,6 +14,9 @@ HuBERT / WavLM / UniSpeech fine-tuning are produced.
   rescore_nbest / rescore_reference   second pass: the n-best list re-ranked with a Transformer LM (unispeech_amd.transformer_lm)
   under the objective of the reference's W2lFairseqLMDecoder; --rescore-lm LM.pt --rescore-dict DICT.txt --rescore-weight W
   --rescore-word-score S on the command line, together with --nbest N
+  NeuralWordLM / fused_lexicon_decode   the Transformer LM inside the first pass (W2lFairseqLMDecoder itself): the search on the
+  host, the LM on the device over a KV-cache tree, a beam's worth of new word histories per frame in one batch;
+  --fuse-lm LM.pt --fuse-dict DICT.txt on the command line (exclusive with --lm and --rescore-lm)
 
 Tables (node 0 is the root; a node is a prefix of a spelling):
   child_off  int32 [N + 1]   node v's children are child_*[child_off[v] : child_off[v + 1]]
@@ -25,8 +28,8 @@ Tables (node 0 is the root; a node is a prefix of a spelling):
 The word LM is ctc_lm.NgramLM(order, entries, symbols=the lexicon's words): its tok_word maps a word id onto the LM's word, a
 word the LM does not list onto <unk>.
 
-Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon, fairseqlm inside
-the first pass (it is the second pass above).  (Time
+Not built: KenLM's binary format, log_add=True, the ASG criterion, a token-level LM together with a lexicon (unit_lm, with an
+n-gram or a Transformer LM), the search itself on the device when the LM is a Transformer.  (Time
 steps: ctc_align.timesteps aligns a hypothesis's tokens.)  The criterion's wer_lexicon / wer_kenlm_model / wer_args stay refused (ctc.CtcCriterion).
 """
 import math
@@ -209,7 +212,7 @@ def _lex_options(word_score, unk_weight):
 
 def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-1, beam=50, beam_size_token=100,
                                   beam_threshold=25.0, lm_weight=0.2, word_score=1.0, unk_weight=-math.inf, sil_weight=0.0,
-                                  nbest=1, normalized=False):
+                                  nbest=1, normalized=False, prepare=None, unequal_margins=None):
     """The lexicon-constrained CTC beam search in float64: the specification of wavlm_ctc_lexbeam (csrc/ctc_lexbeam.hip) and the
     host path of lexicon_beam_decode.  logits [T, B, C] (each frame's log-sum-exp is subtracted unless `normalized`); the LM is
     lexicon.lm (None: every LM score 0).
@@ -239,7 +242,12 @@ def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-
 
     Returns (hyps, margin, abs_sum): per sample the list of (words, tokens, score), words as ids; the smallest score difference
     that decided a merge, a threshold cut, the beam boundary or the order of the returned n-best (inf if nothing was decided);
-    and the sum of the absolute values of the terms of the 1-best's score."""
+    and the sum of the absolute values of the terms of the 1-best's score.
+
+    Two additive hooks, neither of which changes a result: prepare(states), if given, is handed the LM states of the beam at the
+    start of every frame and once more before the end scores (fused_lexicon_decode: a neural LM evaluates them in one batch); unequal_margins, a list, receives per
+    sample the smallest difference among the decisions between scores that are NOT exactly equal (equal scores -- -inf against
+    -inf, one LM entry reached twice -- are settled by the order above whatever the arithmetic)."""
     x = logits.detach().to(torch.float64).cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits, dtype=np.float64)
     T, B, C = x.shape
     beam, ktok, thr, lmw, silw, nbest = ctc._beam_options(C, beam, beam_size_token, beam_threshold, lm_weight, sil_weight, nbest)
@@ -264,20 +272,27 @@ def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-
             e = e - (m + np.log(np.exp(e - m).sum(-1, keepdims=True)))
         if not np.isfinite(e).all():
             raise ValueError("sample %d: the emissions must be finite" % b)
-        margin = math.inf
+        margin = margin_ne = math.inf
+
+        def decided(diff):
+            nonlocal margin, margin_ne
+            margin = min(margin, diff)
+            if diff > 0:
+                margin_ne = min(margin_ne, diff)
         # (score, state, node, token, prev_blank, back = (parent's back, token, word or -1) chain, abs_sum)
         hyps = [(0.0, lm.start if lm is not None else 0, 0, -1, False, None, 0.0)]
         for t in range(il[b]):
             et = e[t]
+            if prepare is not None:
+                prepare([h[1] for h in hyps])
             considered = set(int(c) for c in np.lexsort((np.arange(C), -et))[:ktok])
             cands = {}
 
             def put(r, n, slot, s, a, st, nd, word, back):
-                nonlocal margin
                 key, rank = (st, nd, n), (-s, r, n, slot)           # prev_blank is (n == blank)
                 old = cands.get(key)
                 if old is not None:
-                    margin = min(margin, abs(old[0][0] - rank[0]))
+                    decided(abs(old[0][0] - rank[0]))
                 if old is None or rank < old[0]:
                     cands[key] = (rank, (s, st, nd, n, n == blank, (back, n, word), a))
             for r, (sc, st, nd, tok, pb, back, ab) in enumerate(hyps):
@@ -314,11 +329,14 @@ def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-
                         put(r, n, 1, s + d + usc, a + abs(d) + abs(usc), st2, 0, lx.unk_word, back)
             best = -min(v[0][0] for v in cands.values())
             if thr != math.inf:
-                margin = min([margin] + [abs(-v[0][0] - (best - thr)) for v in cands.values()])
+                for v in cands.values():
+                    decided(abs(-v[0][0] - (best - thr)))
             keep = sorted((v for v in cands.values() if -v[0][0] >= best - thr), key=lambda v: v[0])
             if len(keep) > beam:
-                margin = min(margin, keep[beam - 1][1][0] - keep[beam][1][0])
+                decided(keep[beam - 1][1][0] - keep[beam][1][0])
             hyps = [v[1] for v in keep[:beam]]
+        if prepare is not None:
+            prepare([h[1] for h in hyps])                # the end scores
         if any(h[2] == 0 for h in hyps):
             hyps_fin = [(r, h) for r, h in enumerate(hyps) if h[2] == 0]
         else:
@@ -329,7 +347,7 @@ def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-
             fin.append((-(h[0] + l), r, h, h[6] + abs(l)))
         fin.sort(key=lambda v: v[:2])
         for i in range(min(nbest, len(fin) - 1)):
-            margin = min(margin, fin[i + 1][0] - fin[i][0])
+            decided(fin[i + 1][0] - fin[i][0])
         res = []
         for msc, _, h, _ in fin[:nbest]:
             path, wds, back = [], [], h[5]
@@ -346,6 +364,8 @@ def lexicon_beam_search_reference(logits, input_lengths, lexicon, blank=0, sil=-
             res.append((wds[::-1], seq, -msc))
         out.append(res)
         margins.append(margin)
+        if unequal_margins is not None:
+            unequal_margins.append(margin_ne)
         sums.append(fin[0][3])
     return out, margins, sums
 
@@ -386,6 +406,136 @@ def lexicon_beam_decode(logits, input_lengths, dictionary, lexicon, lm=None, bea
     tokens, counts, scores, n_hyp, words, wcounts = (v.cpu().numpy() for v in res)
     return [[([lexicon.words[int(w)] for w in words[b, h, :wcounts[b, h]]], [int(v) for v in tokens[b, h, :counts[b, h]]],
               float(scores[b, h])) for h in range(int(n_hyp[b]))] for b in range(B)]
+
+
+# ------------------------------------------------------------------------------- a Transformer LM inside the first pass
+class NeuralWordLM:
+    """A transformer_lm.TransformerLM as the word LM of the lexicon search: the protocol ctc_lm.NgramLM gives the lexicon code
+    (start, tok_word, words, score_word(state, id) -> (score, state), score_eos(state)) with the conventions of the reference's
+    FairseqLM (examples/speech_recognition/w2l_decoder.py:288-415): natural log, a lexicon word the LM's dictionary lacks is
+    its unk, and unk scores -inf.  A state is a word history; a history reached twice is one state.
+
+    lm_or_reference: a TransformerLM on the device (its .incremental() is used) or a state store with that interface
+    (transformer_lm.incremental_reference(model): float64 on the CPU).  lm_dictionary: the LM's dictionary.  words: the lexicon's
+    word strings, one per word id.
+
+    score_word names the state after the word without running the network; a state is evaluated when a score is first asked of
+    it.  prepare(states) evaluates, in one batched extend() per depth, every listed state that has no row yet -- the search hands
+    it the beam at the start of a frame.  Of a row of log-probs only the lexicon's columns (the LM entries of its words, and eos)
+    are computed and brought to the host, in float64; prepare(states, only=True) forgets the rows of states that left the beam
+    and drop_rows() all of them (each is rebuilt by one GEMV from the state's hidden row); empty_cache() forgets every state but the start, per utterance as the
+    reference does."""
+
+    def __init__(self, lm_or_reference, lm_dictionary, words):
+        self.store = lm_or_reference if hasattr(lm_or_reference, "extend") else lm_or_reference.incremental()
+        self.words = list(words)
+        self.unk, self.eos = int(lm_dictionary.unk()), int(lm_dictionary.eos())
+        self.tok_word = np.asarray([int(lm_dictionary.index(w)) for w in self.words], dtype=np.int64)
+        self.columns = sorted(set(int(t) for t in self.tok_word) | {self.eos})     # the only entries of a row the search can ask for
+        self._col = {t: i for i, t in enumerate(self.columns)}
+        self.start = 0
+        self.calls = 0                                   # extend() calls since construction
+        self._parent, self._word, self._slot, self._kids, self._rows = [-1], [self.eos], [self.store.start()], [{}], {}
+
+    @property
+    def evaluated(self):
+        """states put through the network since construction (the start included)"""
+        return self.store.evaluated
+
+    def empty_cache(self):
+        self.store.reset()
+        start_row = self._rows.get(0)
+        del self._parent[1:], self._word[1:], self._slot[1:], self._kids[1:]
+        self._kids[0] = {}
+        self._rows = {} if start_row is None else {0: start_row}
+
+    def drop_rows(self):
+        self._rows = {}
+
+    def prepare(self, states, only=False):
+        """only: forget the rows of every other state but the start (the search passes its whole beam: a state that left it is
+        never asked again, and a row costs len(columns) float64 on the host)"""
+        if only:
+            keep = set(int(s) for s in states) | {self.start}
+            self._rows = {s: r for s, r in self._rows.items() if s in keep}
+        todo, seen = [], set()
+        for s in states:
+            s = int(s)
+            while s not in seen and self._slot[s] is None:          # an unevaluated parent comes first
+                seen.add(s)
+                todo.append(s)
+                s = self._parent[s]
+        by_depth = {}
+        for s in todo:
+            d, p = 0, s
+            while self._slot[p] is None:
+                d, p = d + 1, self._parent[p]
+            by_depth.setdefault(d, []).append(s)
+        for d in sorted(by_depth):
+            level = sorted(by_depth[d])
+            new = self.store.extend([self._slot[self._parent[s]] for s in level], [self._word[s] for s in level])
+            self.calls += 1
+            for s, slot in zip(level, new):
+                self._slot[s] = slot
+        need = sorted(set(int(s) for s in states) - set(self._rows))
+        if need:
+            rows = self.store.logprob_rows([self._slot[s] for s in need], self.columns).detach().cpu().to(torch.float64).numpy()
+            for s, row in zip(need, rows):
+                self._rows[s] = row
+
+    def _row(self, state):
+        if state not in self._rows:
+            self.prepare([state])
+        return self._rows[state]
+
+    def score_word(self, state, word):
+        state, word = int(state), int(word)
+        child = self._kids[state].get(word)
+        if child is None:
+            child = self._kids[state][word] = len(self._parent)
+            self._parent.append(state)
+            self._word.append(word)
+            self._slot.append(None)
+            self._kids.append({})
+        if word not in self._col:
+            raise ValueError("word id %d is not an entry of tok_word" % word)
+        return (-math.inf if word == self.unk else float(self._row(state)[self._col[word]])), child
+
+    def score_eos(self, state):
+        return float(self._row(int(state))[self._col[self.eos]])
+
+
+def fused_lexicon_decode(logits, input_lengths, dictionary, lexicon, lm, beam=50, beam_size_token=100, beam_threshold=25.0,
+                         lm_weight=0.2, word_score=1.0, unk_weight=-math.inf, sil_weight=0.0, nbest=1, normalized=False,
+                         blank=None, stats=None):
+    """The lexicon search with a Transformer LM inside the first pass -- the reference's W2lFairseqLMDecoder
+    (examples/speech_recognition/w2l_decoder.py:417-531): the LM scores every word as the search completes it and the trie is
+    smeared with its row at the start state.  lm: the NeuralWordLM the lexicon was built with (lexicon.lm).  The rules are
+    lexicon_beam_search_reference's to the letter -- that function runs, on the host in float64, as flashlight's search runs on
+    the host -- with one addition: each frame first hands the beam's LM states to lm.prepare, so the network evaluates a beam's
+    worth of new word histories per frame in one batch over its KV-cache tree instead of one prefix at a time.  The emissions
+    come to the host once; the LM's cache is emptied per utterance.  stats, a dict, receives per utterance the states evaluated
+    and the extend() calls.  Returns, per sample, a list of at most nbest (word strings, tokens, score), best first."""
+    T, B, C = logits.shape
+    if blank is None:
+        blank = dictionary.bos()
+    if lm is not lexicon.lm or not hasattr(lm, "prepare"):
+        raise ValueError("lm must be the NeuralWordLM the lexicon was built with (lexicon.lm): the trie is smeared with it")
+    sil = ctc.silence_token(dictionary)
+    x = logits.detach().to(torch.float64).cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits, dtype=np.float64)
+    il = [T] * B if input_lengths is None else ctc._host_ints(input_lengths, "input_lengths")
+    out = []
+    for b in range(B):
+        lm.empty_cache()
+        n0, c0 = lm.evaluated, lm.calls
+        hyps = lexicon_beam_search_reference(x[:, b:b + 1], [il[b]], lexicon, blank, sil, beam, beam_size_token, beam_threshold,
+                                             lm_weight, word_score, unk_weight, sil_weight, nbest, normalized,
+                                             prepare=lambda states: lm.prepare(states, only=True))[0][0]
+        out.append([([lexicon.words[w] for w in wds], toks, sc) for wds, toks, sc in hyps])
+        if stats is not None:
+            stats.setdefault("states", []).append(lm.evaluated - n0)
+            stats.setdefault("calls", []).append(lm.calls - c0)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------ rescoring
@@ -463,9 +613,18 @@ def parse_args(argv=None):
         q.add_argument("--rescore-dict", default=None, metavar="DICT.txt", help="the Transformer LM's fairseq dictionary")
         q.add_argument("--rescore-weight", type=float, default=1.0)
         q.add_argument("--rescore-word-score", type=float, default=None, help="default: --word-score")
+        q.add_argument("--fuse-lm", default=None, metavar="LM.pt",
+                       help="Transformer LM checkpoint: the word LM of the first pass (natural log; --lm-weight applies)")
+        q.add_argument("--fuse-dict", default=None, metavar="DICT.txt", help="the fused Transformer LM's fairseq dictionary")
     a = ctc.refuse_binary_lm(p.parse_args(argv))
     if (a.rescore_lm is None) != (a.rescore_dict is None):
         p.error("--rescore-lm and --rescore-dict go together")
+    if (a.fuse_lm is None) != (a.fuse_dict is None):
+        p.error("--fuse-lm and --fuse-dict go together")
+    if a.fuse_lm is not None and a.lm is not None:
+        p.error("--fuse-lm and --lm are exclusive: the first pass has one word LM")
+    if a.fuse_lm is not None and a.rescore_lm is not None:
+        p.error("--fuse-lm and --rescore-lm are exclusive: a fused Transformer LM leaves no second pass")
     return a
 
 
@@ -476,9 +635,18 @@ def _options(a):
 def main(argv=None):
     a = parse_args(argv)
     d = ctc.LetterDictionary.load(a.dict)
-    lexicon = Lexicon.load(a.lexicon, d, a.lm)
     kw = _options(a)
     tlm = None
+    if a.fuse_lm is not None:
+        from .transformer_lm import TransformerLM
+        fd = ctc.LetterDictionary.load(a.fuse_dict)
+        flm = TransformerLM.from_checkpoint(a.fuse_lm, len(fd), pad=fd.pad(), eos=fd.eos(), unk=fd.unk()).cuda()
+        if a.bf16:
+            flm = flm.to(torch.bfloat16)
+        words, spellings = read_lexicon(a.lexicon, d)
+        lexicon = Lexicon(words, spellings, d, NeuralWordLM(flm, fd, words))
+    else:
+        lexicon = Lexicon.load(a.lexicon, d, a.lm)
     if a.rescore_lm is not None:
         from .transformer_lm import TransformerLM
         ld = ctc.LetterDictionary.load(a.rescore_dict)
@@ -488,6 +656,8 @@ def main(argv=None):
         rws = a.word_score if a.rescore_word_score is None else a.rescore_word_score
 
     def search(logits, il, d):                  # the first pass, and the second if a Transformer LM was given
+        if a.fuse_lm is not None:
+            return fused_lexicon_decode(logits, il, d, lexicon, lexicon.lm, **kw)
         hyps = lexicon_beam_decode(logits, il, d, lexicon, lexicon.lm, **kw)
         if tlm is None:
             return hyps

@@ -1019,6 +1019,44 @@ def attn_causal_fwd(qkv, H, lengths=None, scale=None):
     return O
 
 
+def attn_step_supported(head_dim, dtype):
+    return bool(_lib.lib().wavlm_attn_step_supported(int(head_dim), BF16 if dtype == torch.bfloat16 else F32))
+
+
+def attn_step(qkv, kcache, vcache, slot, anc, lengths, H, max_length, scale=None):
+    """one new token per row over a tree-shaped KV cache: qkv [R, 3 * H * d] packed q | k | v (d = 32 or 64), kcache / vcache
+    [slots, H * d] (written at slot[r] by this call), slot int32 [R], anc int32 [R, >= max_length - 1] the slots of each row's
+    ancestors in position order, lengths int32 [R] counting the row itself (<= 0: a row of zeros, nothing stored), max_length the
+    largest of them -> softmax(scale * q [K[anc] ; k]^T) [V[anc] ; v] as [R, H * d]; scale defaults to 1 / sqrt(d).  No row may
+    name a slot another row of the call writes."""
+    dev = _dev(qkv)
+    R, D3 = qkv.shape
+    D = D3 // 3
+    d = D // H
+    if d * 3 * H != D3 or qkv.stride(1) != 1:
+        raise ValueError("qkv width %d is not 3 * %d heads * head_dim with unit channel stride" % (D3, H))
+    for name, c in (("kcache", kcache), ("vcache", vcache)):
+        if c.dim() != 2 or c.shape[1] != D or c.stride(1) != 1 or c.dtype != qkv.dtype or c.device != qkv.device:
+            raise ValueError("%s must be [slots, %d] of qkv's dtype on its device with unit channel stride" % (name, D))
+    if kcache.shape[0] != vcache.shape[0] or kcache.stride(0) != vcache.stride(0):
+        raise ValueError("kcache and vcache must have the same slots and row stride")
+    for name, t in (("slot", slot), ("lengths", lengths)):
+        if t.dtype != torch.int32 or t.numel() != R or not t.is_contiguous() or t.device != qkv.device:
+            raise ValueError("%s must be a contiguous int32 tensor of %d entries on the device of qkv" % (name, R))
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < max(1, int(max_length) - 1) or \
+            (anc.shape[1] > 1 and anc.stride(1) != 1) or anc.device != qkv.device:
+        raise ValueError("anc must be an int32 tensor [%d, >= max(1, max_length - 1)] on the device of qkv" % R)
+    ld_anc = anc.stride(0) if R > 1 else anc.shape[1]
+    O = torch.empty((R, D), dtype=qkv.dtype, device=dev)
+    if R == 0:
+        return O
+    check(_lib.lib().wavlm_attn_step(ptr(qkv), qkv.stride(0), ptr(kcache), ptr(vcache), kcache.stride(0), kcache.shape[0],
+                                     ptr(slot), ptr(anc), ld_anc, ptr(lengths), int(max_length), ptr(O), O.stride(0), R, H, d, dt(qkv),
+                                     float(scale if scale is not None else d ** -0.5), stream()),
+          "wavlm_attn_step[R=%d H=%d d=%d max_length=%d]" % (R, H, d, max_length))
+    return O
+
+
 # ---------------------------------------------------------------------------------------------- CTC
 def _ctc_view(logits):
     """(stride_b, stride_t) in elements of a [B, T, C]-indexed view with unit class stride"""

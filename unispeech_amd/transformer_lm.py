@@ -16,6 +16,11 @@ models/transformer.py) scored the way `FairseqLM` of examples/speech_recognition
                     log p(eos | eos).  Sentences are sorted by length, batched right-padded in at most `max_tokens` rows, and only
                     the hidden rows that have a target reach the output layer.
   score_reference   the same rules in float64 torch on the CPU: the specification.
+  incremental()     IncrementalStates: decoder states over a tree of word histories with a KV cache (csrc/lm_step.hip
+                    wavlm_attn_step), a beam's worth of new states per call -- what the first pass of
+                    ctc_lexicon.fused_lexicon_decode asks for.  The reference's FairseqLM has no working cache
+                    (`save_incremental = False`, w2l_decoder.py:298) and re-runs the whole prefix per state.
+  incremental_reference   the same interface in float64 on the CPU: the specification.
   python -m unispeech_amd.transformer_lm score LM.pt DICT.txt [FILE]
 
 How a layer runs: wavlm_gemm (bias, GELU and residual epilogues; q|k|v packed once into a single GEMM), wavlm_act_fwd for ReLU,
@@ -32,7 +37,8 @@ import sys
 import torch
 import torch.nn as nn
 
-__all__ = ["TransformerLM", "TransformerLMConfig", "score_reference", "lm_logprob", "sinusoidal_table"]
+__all__ = ["TransformerLM", "TransformerLMConfig", "score_reference", "lm_logprob", "sinusoidal_table", "IncrementalStates",
+           "incremental_reference"]
 
 COMPOSED_BUDGET_BYTES = 256 << 20      # fp32 logits of one row chunk of the composed output layer
 REFUSED = ("character_embeddings", "base_layers", "cross_self_attention", "tie_adaptive_weights")
@@ -270,10 +276,20 @@ class TransformerLM(nn.Module):
         """tokens int32 [B, T] on the device, right-padded with pad; lengths int32 [B] -> the decoder's features [B * T,
         decoder_output_dim] (extract_features, transformer.py:846-963); rows beyond a length hold nothing of use"""
         from . import ops
-        cfg, d, im = self.cfg, self.decoder, self._images()
         B, T = tokens.shape
-        M, D, H = B * T, cfg.decoder_embed_dim, cfg.decoder_attention_heads
-        dev, dtype = tokens.device, d.output_projection.weight.dtype
+        H = self.cfg.decoder_attention_heads
+        ar = torch.arange(T, dtype=torch.int32, device=tokens.device).unsqueeze(0)
+        pidx = torch.where(ar < lengths.unsqueeze(1), ar + (self.pad + 1), torch.full_like(ar, self.pad)).reshape(-1)
+        return self._stack(tokens.reshape(-1), pidx.contiguous(), T,
+                           lambda i, qkv: ops.attn_causal_fwd(qkv.view(B, T, -1), H, lengths).view(B * T, -1))
+
+    def _stack(self, flat, pidx, T, attention):
+        """the decoder over M rows that meet only in `attention(layer, qkv [M, 3 D]) -> [M, D]`: flat int32 [M] the tokens, pidx
+        int32 [M] their rows of the position table, which covers T tokens"""
+        from . import ops
+        cfg, d, im = self.cfg, self.decoder, self._images()
+        M, D = flat.numel(), cfg.decoder_embed_dim
+        dev, dtype = flat.device, d.output_projection.weight.dtype
         new = lambda *shape: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
 
         def linear(x, w, b, K, N, epi=0, res=None):
@@ -284,15 +300,12 @@ class TransformerLM(nn.Module):
         def ln(x, r, mod):
             return ops.layernorm_fwd(x, r, mod.weight, mod.bias, mod.eps, save=False)[0]
 
-        flat = tokens.reshape(-1)
         x = ops.gather_rows(im["embed"], flat, M)
         if hasattr(d, "project_in_dim"):
             x = linear(x, d.project_in_dim.weight, None, x.shape[1], D)
         pos = self._positions(im, T)
         if pos is not None:
-            ar = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(0)
-            pidx = torch.where(ar < lengths.unsqueeze(1), ar + (self.pad + 1), torch.full_like(ar, self.pad)).reshape(-1)
-            ops.axpby_(x, ops.gather_rows(pos, pidx.contiguous(), M), 1.0, 1.0)
+            ops.axpby_(x, ops.gather_rows(pos, pidx, M), 1.0, 1.0)
         if cfg.layernorm_embedding:
             x = ln(x, None, d.layernorm_embedding)
         pre, F = cfg.decoder_normalize_before, cfg.decoder_ffn_embed_dim
@@ -300,12 +313,12 @@ class TransformerLM(nn.Module):
             a = l.self_attn
             h = ln(x, None, l.self_attn_layer_norm) if pre else x
             qkv = linear(h, im["qkv_w%d" % i], im["qkv_b%d" % i], D, 3 * D)
-            o = ops.attn_causal_fwd(qkv.view(B, T, 3 * D), H, lengths)
+            o = attention(i, qkv)
             if pre:
-                x = linear(o.view(M, D), a.out_proj.weight, a.out_proj.bias, D, D, res=x)
+                x = linear(o, a.out_proj.weight, a.out_proj.bias, D, D, res=x)
                 h = ln(x, None, l.final_layer_norm)
             else:
-                x = ln(x, linear(o.view(M, D), a.out_proj.weight, a.out_proj.bias, D, D), l.self_attn_layer_norm)
+                x = ln(x, linear(o, a.out_proj.weight, a.out_proj.bias, D, D), l.self_attn_layer_norm)
                 h = x
             if cfg.activation_fn == "gelu":
                 f = linear(h, l.fc1.weight, l.fc1.bias, D, F, epi=1)
@@ -372,6 +385,149 @@ class TransformerLM(nn.Module):
                     out[i, t] = -math.inf
         return out, out.sum(1)
 
+    def incremental(self, chunk=1024):
+        """a store of decoder states over a tree of word histories (IncrementalStates): the first pass of a beam search asks for
+        the next-word distribution of many histories that share prefixes, a few more per frame"""
+        return IncrementalStates(self, chunk)
+
+
+def _check_extension(model, depth, words):
+    """the new states' tokens count depth + 1 each"""
+    for w in words:
+        if not 0 <= int(w) < model.vocab:
+            raise ValueError("word id %r is not one of the %d dictionary entries" % (w, model.vocab))
+    if len(depth) and max(depth) + 1 > model.cfg.max_target_positions:
+        raise ValueError("a history of %d tokens is longer than max_target_positions = %d"
+                         % (max(depth) + 1, model.cfg.max_target_positions))
+
+
+class IncrementalStates:
+    """TransformerLM.incremental(): incremental decoding with a KV cache shaped as a tree.  A state is a word history [eos, w_1 ..
+    w_n]; its id is its cache slot.  Kept per state: the K and V rows of its last token in every layer, the decoder's final
+    hidden row and the log-sum-exp of its logits -- so a row of log-probs is one GEMV away and need not be kept.
+
+      start()                    the state of [eos]
+      extend(parents, words)     new state ids, one per (parent, word): one row per new state through every layer in one batch
+                                 (wavlm_gemm / wavlm_layernorm_fwd / wavlm_act_fwd as in score(), wavlm_attn_step in place of the
+                                 causal attention); the position is the state's depth
+      logprob_rows(states, columns=None)   fp32 [n, V] (or [n, len(columns)]) natural-log probabilities on the device
+      reset()                    drops everything but the start state
+    The caches grow in chunks of `chunk` slots (doubling), never per state."""
+
+    def __init__(self, model, chunk=1024):
+        self.model, self.chunk = model, int(chunk)
+        w = model.decoder.output_projection.weight
+        from . import ops
+        self.device, self.dtype = ops._dev(w), w.dtype
+        cfg = model.cfg
+        if not ops.attn_step_supported(cfg.decoder_embed_dim // cfg.decoder_attention_heads, self.dtype):
+            raise NotImplementedError("wavlm_attn_step does not take heads %d wide in %s"
+                                      % (cfg.decoder_embed_dim // cfg.decoder_attention_heads, self.dtype))
+        if not ops.lm_logprob_supported(w.shape[1], model.vocab, self.dtype):
+            raise NotImplementedError("wavlm_lm_logprob does not take decoder_output_dim = %d: no lse per state" % w.shape[1])
+        self.cap = 0
+        self.kc, self.vc, self.hidden, self.lse = [], [], None, None
+        self.parent, self.depth, self.chain = [], [], []
+        self.evaluated = 0                                       # states put through the network since construction
+        self._wcols = None                                       # (columns, the output projection, its rows at those columns)
+        self._grow(self.chunk)
+        self._run([-1], [model.eos])
+
+    def __len__(self):
+        return len(self.parent)
+
+    def _grow(self, need):
+        if need <= self.cap:
+            return
+        cap = max(need, 2 * self.cap)
+        cap = (cap + self.chunk - 1) // self.chunk * self.chunk
+        cfg, n = self.model.cfg, len(self.parent)
+
+        def grown(old, width, dtype):
+            t = torch.zeros((cap, width) if width else (cap,), dtype=dtype, device=self.device)
+            if old is not None and n:
+                t[:n] = old[:n]
+            return t
+        L = cfg.decoder_layers
+        self.kc = [grown(self.kc[i] if self.kc else None, cfg.decoder_embed_dim, self.dtype) for i in range(L)]
+        self.vc = [grown(self.vc[i] if self.vc else None, cfg.decoder_embed_dim, self.dtype) for i in range(L)]
+        self.hidden = grown(self.hidden, self.model.decoder.output_projection.weight.shape[1], self.dtype)
+        self.lse = grown(self.lse, 0, torch.float32)
+        self.cap = cap
+
+    def start(self):
+        return 0
+
+    def reset(self):
+        del self.parent[1:], self.depth[1:], self.chain[1:]
+
+    def _run(self, parents, words):
+        from . import ops
+        m, cfg = self.model, self.model.cfg
+        R, n0 = len(words), len(self.parent)
+        depth = [self.depth[p] + 1 if p >= 0 else 0 for p in parents]
+        _check_extension(m, depth, words)
+        self._grow(n0 + R)
+        chains = [self.chain[p] + [p] if p >= 0 else [] for p in parents]
+        Lmax = max(depth) + 1
+        anc = torch.zeros((R, max(1, Lmax - 1)), dtype=torch.int32)
+        for r, c in enumerate(chains):
+            anc[r, :len(c)] = torch.tensor(c, dtype=torch.int32)
+        dev = self.device
+        anc = anc.to(dev)
+        slot = torch.arange(n0, n0 + R, dtype=torch.int32).to(dev)
+        lengths = torch.tensor([x + 1 for x in depth], dtype=torch.int32).to(dev)
+        flat = torch.tensor([int(w) for w in words], dtype=torch.int32).to(dev)
+        pidx = (lengths + m.pad).contiguous()                    # position row pad + 1 + depth
+        H = cfg.decoder_attention_heads
+        with torch.no_grad():
+            x = m._stack(flat, pidx, Lmax, lambda i, qkv: ops.attn_step(qkv, self.kc[i], self.vc[i], slot, anc, lengths, H, Lmax))
+            self.hidden[n0:n0 + R] = x
+            none = torch.full((R,), -1, dtype=torch.int32, device=dev)
+            # the kernel itself, whatever WAVLM_LM_LOGPROB_COMPOSED says: the composed output layer returns no lse
+            self.lse[n0:n0 + R] = ops.lm_logprob(x, m.decoder.output_projection.weight, none, want_lse=True)[1]
+        self.parent += list(parents)
+        self.depth += depth
+        self.chain += chains
+        self.evaluated += R
+        return list(range(n0, n0 + R))
+
+    def extend(self, parents, words):
+        parents = [int(p) for p in parents]
+        if len(parents) != len(words):
+            raise ValueError("%d parents for %d words" % (len(parents), len(words)))
+        for p in parents:
+            if not 0 <= p < len(self.parent):
+                raise ValueError("state %r is not one of the %d states" % (p, len(self.parent)))
+        return self._run(parents, words) if parents else []
+
+    def logprob_rows(self, states, columns=None):
+        from . import ops
+        states = [int(s) for s in states]
+        for s in states:
+            if not 0 <= s < len(self.parent):
+                raise ValueError("state %r is not one of the %d states" % (s, len(self.parent)))
+        w, dev, n = self.model.decoder.output_projection.weight, self.device, len(states)
+        idx = torch.tensor(states, dtype=torch.int32).to(dev)
+        if columns is not None:
+            columns = [int(c) for c in columns]
+            if columns and not (0 <= min(columns) and max(columns) < self.model.vocab):
+                raise ValueError("a column is not one of the %d dictionary entries" % self.model.vocab)
+        V = w.shape[0] if columns is None else len(columns)
+        if n == 0 or V == 0:
+            return torch.zeros((n, V), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            x = ops.gather_rows(self.hidden, idx, n)
+            if columns is not None:
+                if self._wcols is None or self._wcols[0] != columns or self._wcols[1] is not w:     # a scorer asks for one set
+                    cols = torch.tensor(columns, dtype=torch.int32).to(dev)
+                    self._wcols = (columns, w, ops.gather_rows(w, cols, V))
+                w = self._wcols[2]
+            ld = (V + 3) // 4 * 4
+            logits = torch.empty((n, ld), dtype=torch.float32, device=dev)
+            ops.gemm(x, w, logits, n, V, x.shape[1], lda=x.stride(0), ldb=w.stride(0), ldc=ld)
+            return logits[:, :V] - self.lse[idx.long()].unsqueeze(1)
+
 
 def composed_switch():
     return os.environ.get("WAVLM_LM_LOGPROB_COMPOSED", "") not in ("", "0")
@@ -417,10 +573,11 @@ def _lin64(x, mod):
     return y + mod.bias.double() if mod.bias is not None else y
 
 
-def _forward64(model, words):
-    """one sentence, no padding: [eos, w_1 .. w_n] -> log-probs [n + 1, V] in float64"""
+def _decoder64(model, tok, first, attend):
+    """the decoder in float64 over the T tokens `tok` (a long tensor) at positions first .. first + T - 1, meeting only in
+    attend(layer, q [T, D] scaled, k [T, D], v [T, D]) -> [T, D]: -> log-probs [T, V].  The one specification: _forward64 attends
+    causally within the T tokens, incremental_reference over the rows its ancestors left behind."""
     cfg, d = model.cfg, model.decoder
-    tok = torch.tensor([model.eos] + list(words), dtype=torch.long)
     T, D, H = tok.numel(), cfg.decoder_embed_dim, cfg.decoder_attention_heads
     if cfg.adaptive_input:
         x = torch.zeros(T, D, dtype=torch.float64)
@@ -436,22 +593,17 @@ def _forward64(model, words):
     if hasattr(d, "project_in_dim"):
         x = _lin64(x, d.project_in_dim)
     if not cfg.no_token_positional_embeddings:
-        idx = torch.arange(T) + model.pad + 1                    # make_positions: no padding in a single sentence
-        tab = d.embed_positions.weight if cfg.decoder_learned_pos else sinusoidal_table(model.pad + 1 + T, D, model.pad)
+        idx = torch.arange(first, first + T) + model.pad + 1     # make_positions: no padding in a single sentence
+        tab = d.embed_positions.weight if cfg.decoder_learned_pos else sinusoidal_table(model.pad + 1 + first + T, D, model.pad)
         x = x + tab.double()[idx]
     if cfg.layernorm_embedding:
         x = _ln64(x, d.layernorm_embedding)
     hd = D // H
-    future = torch.triu(torch.ones(T, T, dtype=torch.bool), 1)
     pre = cfg.decoder_normalize_before
-    for l in d.layers:
+    for i, l in enumerate(d.layers):
         a = l.self_attn
         h = _ln64(x, l.self_attn_layer_norm) if pre else x
-        q = (_lin64(h, a.q_proj) * hd ** -0.5).view(T, H, hd).transpose(0, 1)
-        k = _lin64(h, a.k_proj).view(T, H, hd).transpose(0, 1)
-        v = _lin64(h, a.v_proj).view(T, H, hd).transpose(0, 1)
-        s = (q @ k.transpose(1, 2)).masked_fill(future, -math.inf)
-        o = (torch.softmax(s, -1) @ v).transpose(0, 1).reshape(T, D)
+        o = attend(i, _lin64(h, a.q_proj) * hd ** -0.5, _lin64(h, a.k_proj), _lin64(h, a.v_proj))
         x = x + _lin64(o, a.out_proj)
         if not pre:
             x = _ln64(x, l.self_attn_layer_norm)
@@ -465,7 +617,26 @@ def _forward64(model, words):
         x = _ln64(x, d.layer_norm)
     if hasattr(d, "project_out_dim"):
         x = _lin64(x, d.project_out_dim)
-    return torch.log_softmax(x @ d.output_projection.weight.double().t(), -1)
+    return x
+
+
+def _attend64(q, k, v, H, future=None):
+    """softmax(q k^T) v per head: q [Tq, D], k and v [Tk, D]; future: a bool mask [Tq, Tk] of the pairs that do not attend"""
+    Tq, Tk, hd = q.shape[0], k.shape[0], q.shape[1] // H
+    q, k, v = (t.view(-1, H, hd).transpose(0, 1) for t in (q, k, v))
+    s = q @ k.transpose(1, 2)
+    if future is not None:
+        s = s.masked_fill(future, -math.inf)
+    return (torch.softmax(s, -1) @ v).transpose(0, 1).reshape(Tq, H * hd)
+
+
+def _forward64(model, words):
+    """one sentence, no padding: [eos, w_1 .. w_n] -> log-probs [n + 1, V] in float64"""
+    tok = torch.tensor([model.eos] + list(words), dtype=torch.long)
+    T, H = tok.numel(), model.cfg.decoder_attention_heads
+    future = torch.triu(torch.ones(T, T, dtype=torch.bool), 1)
+    x = _decoder64(model, tok, 0, lambda i, q, k, v: _attend64(q, k, v, H, future))
+    return torch.log_softmax(x @ model.decoder.output_projection.weight.double().t(), -1)
 
 
 def score_reference(model, sentences):
@@ -482,6 +653,74 @@ def score_reference(model, sentences):
             lp[tgt == model.unk] = -math.inf
             out[i, :tgt.numel()] = lp
     return out, out.sum(1)
+
+
+class _ReferenceStates:
+    """incremental_reference(model): IncrementalStates' interface in float64 on the CPU, one state at a time, through _decoder64
+    -- the new token's row through every layer, its attention over the K and V rows its ancestors left behind"""
+
+    def __init__(self, model):
+        self.model = model
+        self.parent, self.depth, self.kv, self.hidden = [], [], [], []
+        self.evaluated = 0
+        self._one(-1, model.eos)
+
+    def __len__(self):
+        return len(self.parent)
+
+    def start(self):
+        return 0
+
+    def reset(self):
+        del self.parent[1:], self.depth[1:], self.kv[1:], self.hidden[1:]
+
+    def _one(self, parent, word):
+        H = self.model.cfg.decoder_attention_heads
+        depth = self.depth[parent] + 1 if parent >= 0 else 0
+        chain, p = [], parent
+        while p >= 0:
+            chain.append(p)
+            p = self.parent[p]
+        chain.reverse()
+        kv = []
+
+        def attend(i, q, k1, v1):
+            kv.append((k1, v1))
+            return _attend64(q, torch.cat([self.kv[s][i][0] for s in chain] + [k1]),
+                             torch.cat([self.kv[s][i][1] for s in chain] + [v1]), H)
+        x = _decoder64(self.model, torch.tensor([int(word)], dtype=torch.long), depth, attend)
+        self.parent.append(parent)
+        self.depth.append(depth)
+        self.kv.append(kv)
+        self.hidden.append(x)
+        self.evaluated += 1
+        return len(self.parent) - 1
+
+    def extend(self, parents, words):
+        parents = [int(p) for p in parents]
+        if len(parents) != len(words):
+            raise ValueError("%d parents for %d words" % (len(parents), len(words)))
+        for p in parents:
+            if not 0 <= p < len(self.parent):
+                raise ValueError("state %r is not one of the %d states" % (p, len(self.parent)))
+        _check_extension(self.model, [self.depth[p] + 1 for p in parents], words)
+        with torch.no_grad():
+            return [self._one(p, w) for p, w in zip(parents, words)]
+
+    def logprob_rows(self, states, columns=None):
+        w = self.model.decoder.output_projection.weight.double()
+        with torch.no_grad():
+            if not len(states):
+                return torch.zeros(0, w.shape[0] if columns is None else len(columns), dtype=torch.float64)
+            lp = torch.cat([torch.log_softmax(self.hidden[int(s)] @ w.t(), -1) for s in states])    # row by row: no row
+            #                                                                                  depends on its company
+        return lp if columns is None else lp[:, torch.tensor([int(c) for c in columns], dtype=torch.long)]
+
+
+def incremental_reference(model):
+    """TransformerLM.incremental()'s interface in float64 on the CPU: the specification"""
+    with torch.no_grad():
+        return _ReferenceStates(model)
 
 
 # --------------------------------------------------------------------------------------------------------- command line
