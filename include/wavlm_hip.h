@@ -953,6 +953,77 @@ int wavlm_attn_step(const void* qkv, int64_t ld_qkv, void* Kc, void* Vc, int64_t
                     int32_t R, int32_t H, int32_t head_dim, int32_t dtype, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Seq2seq ASR decoding (csrc/s2s.hip; additive to ABI 30: five new symbols, nothing else changes).
+ *   wavlm_attn_cross_fwd  encoder-decoder attention: a few query rows per sentence over its encoder frames.  Q [R, H * d] (row
+ *                         stride ld_q); KV [B, Ts, 2 * H * d], a frame's keys then its values (batch stride s_kv, row stride
+ *                         ld_kv); src_lengths int32 [B] on the device (NULL: every sentence is Ts long; values are clamped to
+ *                         [0, Ts]); row_offsets int32 [B + 1]: rows row_offsets[b] .. row_offsets[b + 1] - 1 attend sentence b
+ *                         (a group may be empty; rows that no group names are not written); live int32 [R] or NULL: a row
+ *                         with live[r] <= 0 is written as zeros and reads nothing; O [R, H * d] (row stride ld_o).
+ *                           O[r, h] = softmax(scale * q[r, h] . K[b, 0 .. len_b - 1, h]) V[b, 0 .. len_b - 1, h]
+ *                         fp32 softmax state and accumulation, online softmax, no score tensor; keys at or beyond
+ *                         src_lengths[b] are never read; src_lengths[b] <= 0 gives rows of zeros.  One workgroup owns
+ *                         (sentence, head, tile of up to 32 rows) and walks K and V once for the tile: the rows of a sentence
+ *                         share the pass.  Its four waves split the keys by the key index alone and are folded through LDS in
+ *                         wave order; bf16: both products on v_mfma_f32_32x32x16_bf16 (keys x queries: a query's softmax
+ *                         state sits on a lane), fp32: FMA in channel order.  No atomics.  Bitwise reproducible; a row's bits
+ *                         depend neither on the other rows of its group, nor on the group's size, nor on B, nor on its place
+ *                         in the batch.  max_group >= 1 sizes the grid: the largest group the caller expects (B * H *
+ *                         ceil(min(max_group, R) / 32) workgroups); a larger group is still computed in full, its workgroups
+ *                         taking several tiles each, with the same bits.  head_dim 32 or 64, WL_F32 or WL_BF16, any Ts >= 1.
+ *                         Offsets that are not non-decreasing or leave [0, R] form no address: the rows between the two
+ *                         offending entries (clamped to [0, R)) come back as NaN -- except a row that a sound group names as
+ *                         well: two workgroups write it, and it holds either that group's result or NaN (unspecified which).
+ *                         A tile whose rows are all dead (live <= 0) reads neither Q nor K nor V.
+ *                         Returns -1 before any launch for a NULL pointer (src_lengths and live excepted), Q / KV / O or a
+ *                         stride of theirs that is not 16-byte aligned, an int32 array that is not 4-byte aligned, ld_q or ld_o
+ *                         below H * d, ld_kv below 2 * H * d, s_kv shorter than a sentence, two of Q / KV / O whose byte ranges
+ *                         overlap, an unsupported head width or dtype, R, B, Ts, H or max_group below 1, or a grid beyond one
+ *                         dimension.
+ *   wavlm_beam_step       one step of SequenceGenerator._generate (src/fairseq/sequence_generator.py:326-560) with
+ *                         BeamSearch.step (src/fairseq/search.py:103-147) for every sentence; one workgroup per sentence.  Rows
+ *                         are r = b * beam + k; sentence b has n_live[b] live rows k < n_live[b] (1 at step 0, up to beam
+ *                         afterwards, 0 once finished).  logits [B * beam, V] (dtype, row stride ld_logits; rows that are not
+ *                         live are not read; an entry of -inf is a token of probability 0, a NaN or +inf entry makes its whole
+ *                         row -inf, as torch.log_softmax followed by line 346 does), cum fp32 [B * beam] the rows' cumulative scores (0 at step 0).  In order: the
+ *                         logits over `temperature`, log-softmax in fp32 (811-815); NaN -> -inf (346); pad -> -inf, unk -=
+ *                         unk_penalty (348-349); at step >= max_len everything but eos -> -inf (352-354); at step < min_len
+ *                         eos -> -inf (365-367); + cum[row]; the best min(2 beam, n_live V - 1) of the sentence by (score
+ *                         descending, k * V + token ascending) -- torch.topk leaves ties open, this does not.  The walk
+ *                         (405-520): an eos (with a score above -inf) among the first `beam` ranks goes to the finished list
+ *                         while that has fewer than `beam` entries: fin_f [B, beam, 3] = (score / (step + 1)^len_penalty if
+ *                         normalize_scores else score, score, score - parent's cum), fin_i [B, beam, 2] = (parent slot,
+ *                         length = step + 1), n_fin [B]; an eos at a later rank is dropped.  The first `beam` others become
+ *                         the next step's rows k' = 0, 1, ..: tokens[r], cum[r], lengths[r] = step + 2, slots[r] = ((step + 1)
+ *                         B + b) beam + k' (static: a row's slot in a KV cache of wavlm_attn_step and in the tree),
+ *                         anc_out[r, 0 .. step] = anc_in[parent row, 0 .. step - 1] then the parent's slot (step B + b) beam +
+ *                         k (two buffers, ping-pong, row stride ld_anc >= step + 1), tree_parent / tree_token / tree_score
+ *                         [tree_slots] at the new slot (score: the step's own, new cum - parent's cum, as finalize_hypos
+ *                         takes positional scores).  Rows beyond them get lengths 0, token pad, cum -inf.  A sentence with
+ *                         `beam` finished entries, or at step >= max_len, or without a candidate left, gets n_live = 0 and
+ *                         *finished (int32, device) goes up by one (715-735) -- the only global atomic.  workspace holds the
+ *                         candidates for inspection: fp32 scores [B, 2 beam], int32 flat indices [B, 2 beam], int32 counts
+ *                         [B] (wavlm_beam_step_workspace_bytes, 16-byte aligned).  Bitwise reproducible; a sentence's result
+ *                         depends neither on B nor on its place in the batch.
+ *                         wavlm_beam_step_supported (host): 1 for 1 <= beam <= 32, 2 <= V <= 65536, 1 <= B <= 65535 and the two
+ *                         dtypes.  Returns -1 before the launch otherwise, and for a NULL pointer, anc_in == anc_out, ld_logits <
+ *                         V, ld_anc < step + 1, tree_slots < (step + 2) B beam, temperature <= 0, a negative step or max_len, or
+ *                         a short or misaligned workspace.
+ * ------------------------------------------------------------------------------------------ */
+int wavlm_attn_cross_fwd_supported(int32_t head_dim, int32_t dtype);
+int wavlm_attn_cross_fwd(const void* Q, int64_t ld_q, const void* KV, int64_t s_kv, int64_t ld_kv, const int32_t* src_lengths,
+                         const int32_t* row_offsets, const int32_t* live, void* O, int64_t ld_o, int32_t R, int32_t B, int32_t Ts,
+                         int32_t H, int32_t head_dim, int32_t dtype, float scale, int32_t max_group, void* stream);
+int wavlm_beam_step_supported(int32_t beam, int32_t V, int32_t B, int32_t dtype);
+uint64_t wavlm_beam_step_workspace_bytes(int32_t B, int32_t beam);
+int wavlm_beam_step(const void* logits, int64_t ld_logits, int32_t dtype, float* cum, int32_t* n_live, int32_t* tokens,
+                    int32_t* lengths, int32_t* slots, const int32_t* anc_in, int32_t* anc_out, int64_t ld_anc,
+                    int32_t* tree_parent, int32_t* tree_token, float* tree_score, int64_t tree_slots, float* fin_f, int32_t* fin_i,
+                    int32_t* n_fin, int32_t* finished, int32_t B, int32_t beam, int32_t V, int32_t step, int32_t max_len,
+                    int32_t min_len, int32_t pad, int32_t unk, int32_t eos, float unk_penalty, float temperature,
+                    float len_penalty, int32_t normalize_scores, void* workspace, uint64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.
  * ------------------------------------------------------------------------------------------ */
 void wavlm_prof_enable(int on);

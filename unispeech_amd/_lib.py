@@ -248,6 +248,14 @@ SIGNATURES = {
     "wavlm_attn_step_supported": (c_i32, [c_i32, c_i32]),
     "wavlm_attn_step": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32,
                                 c_i32, c_i32, c_f32, c_vp]),
+    "wavlm_attn_cross_fwd_supported": (c_i32, [c_i32, c_i32]),
+    "wavlm_attn_cross_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32,
+                                     c_i32, c_i32, c_f32, c_i32, c_vp]),
+    "wavlm_beam_step_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "wavlm_beam_step_workspace_bytes": (c_u64, [c_i32, c_i32]),
+    "wavlm_beam_step": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
+                                c_f32, c_i32, c_vp, c_u64, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

@@ -17,8 +17,9 @@ The lexicon / word-LM decoder (w2l_decoder.py with --lexicon) is unispeech_amd.c
 python -m unispeech_amd.ctc_lexicon {decode,score} ... --lexicon FILE [--lm FILE.arpa]; these two sub-commands take no lexicon.
 
 Not built, refused by name: KenLM's binary format, the criterion's decoder options
-(wer_kenlm_model, wer_lexicon, wer_args), reduce=False, and the seq2seq models of hubert_asr.py / wav2vec2_asr.py.  (The UniSpeech multitask model and criterion are unispeech_amd.unispeech;
-a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
+(wer_kenlm_model, wer_lexicon, wer_args), reduce=False, and the seq2seq `decoder_*` options: EncoderCtc is the CTC model only.  (The
+seq2seq model of wav2vec2_asr.py is unispeech_amd.seq2seq, inference only; training it is not built.  The UniSpeech multitask model
+and criterion are unispeech_amd.unispeech; a checkpoint of theirs is fine-tuned through EncoderCtc.build(arch="unispeech").)
 
 Tensors on the host take ctc_reference (loss) and numpy (decode): that path exists for the tests and for tiny inputs.  A device
 tensor always takes the kernels, and a kernel that is missing or refuses its arguments is an error, never a detour.  The one
@@ -757,7 +758,7 @@ OVERRIDES = {"dropout_input": "dropout_input", "dropout": "dropout", "attention_
              "mask_channel_selection": "mask_channel_selection", "mask_channel_other": "mask_channel_other",
              "no_mask_channel_overlap": "no_mask_channel_overlap", "layerdrop": "encoder_layerdrop"}
 REFUSED = {"no_pretrained_weights": False, "normalize": False, "data": None, "w2v_args": None, "w2v_path": None,
-           # HubertSeq2SeqConfig / Wav2Vec2Seq2SeqConfig: the seq2seq models are not built
+           # HubertSeq2SeqConfig / Wav2Vec2Seq2SeqConfig: not this wrapper's (unispeech_amd.seq2seq takes them)
            "decoder_embed_dim": 768, "decoder_ffn_embed_dim": 3072, "decoder_layers": 6, "decoder_layerdrop": 0.0,
            "decoder_attention_heads": 4, "decoder_learned_pos": False, "decoder_normalize_before": False,
            "no_token_positional_embeddings": False, "decoder_dropout": 0.0, "decoder_attention_dropout": 0.0,

@@ -1057,6 +1057,111 @@ def attn_step(qkv, kcache, vcache, slot, anc, lengths, H, max_length, scale=None
     return O
 
 
+# ------------------------------------------------------------------------------------ seq2seq decoding
+def attn_cross_fwd_supported(head_dim, dtype):
+    return bool(_lib.lib().wavlm_attn_cross_fwd_supported(int(head_dim), BF16 if dtype == torch.bfloat16 else F32))
+
+
+def _i32(name, t, n, dev):
+    if t is not None and (t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != dev):
+        raise ValueError("%s must be a contiguous int32 tensor of %d entries on the device of the other arguments" % (name, n))
+
+
+def attn_cross_fwd(q, kv, H, row_offsets, src_lengths=None, live=None, max_group=None, scale=None, out=None):
+    """q [R, H * d] (d = 32 or 64, any row stride), kv [B, Ts, 2 * H * d] a frame's keys then its values (any batch and row
+    stride), row_offsets int32 [B + 1]: rows row_offsets[b] .. row_offsets[b + 1] - 1 attend sentence b; src_lengths int32 [B]
+    (None: Ts); live int32 [R] (None: all; <= 0: a row of zeros that reads nothing) -> softmax(scale * q K_b^T) V_b as [R, H * d].
+    max_group: the largest group expected (sizes the grid; None: R); scale defaults to 1 / sqrt(d).  The rows of a sentence share
+    one pass over its keys and values."""
+    dev = _dev(q)
+    if q.dim() != 2 or kv.dim() != 3 or q.stride(1) != 1 or kv.stride(2) != 1 or q.dtype != kv.dtype or kv.device != dev:
+        raise ValueError("q [R, H * d] and kv [B, Ts, 2 * H * d] must share a dtype and a device, with unit channel stride")
+    R, D = q.shape
+    B, Ts, D2 = kv.shape
+    d = D // H
+    if d * H != D or D2 != 2 * D:
+        raise ValueError("q width %d is not %d heads * head_dim, or kv width %d is not twice that" % (D, H, D2))
+    _i32("row_offsets", row_offsets, B + 1, dev)
+    _i32("src_lengths", src_lengths, B, dev)
+    _i32("live", live, R, dev)
+    if row_offsets is None:
+        raise ValueError("row_offsets is needed")
+    O = torch.empty((R, D), dtype=q.dtype, device=dev) if out is None else out
+    if O.shape != (R, D) or O.dtype != q.dtype or O.stride(1) != 1 or O.device != dev:
+        raise ValueError("out must be [%d, %d] of q's dtype on its device with unit channel stride" % (R, D))
+    if R == 0:
+        return O
+    check(_lib.lib().wavlm_attn_cross_fwd(ptr(q), q.stride(0) if R > 1 else max(q.stride(0), D), ptr(kv),
+                                          kv.stride(0) if B > 1 else max(kv.stride(0), Ts * kv.stride(1)), kv.stride(1),
+                                          ptr(src_lengths), ptr(row_offsets), ptr(live), ptr(O),
+                                          O.stride(0) if R > 1 else max(O.stride(0), D), R, B, Ts, H, d, dt(q),
+                                          float(scale if scale is not None else d ** -0.5),
+                                          int(max_group if max_group is not None else R), stream()),
+          "wavlm_attn_cross_fwd[R=%d B=%d Ts=%d H=%d d=%d]" % (R, B, Ts, H, d))
+    return O
+
+
+def beam_step_supported(beam, V, B, dtype):
+    return bool(_lib.lib().wavlm_beam_step_supported(int(beam), int(V), int(B), BF16 if dtype == torch.bfloat16 else F32))
+
+
+class BeamState:
+    """the device state wavlm_beam_step works on, for B sentences x `beam` rows and steps 0 .. max_len: cum, n_live, tokens,
+    lengths, slots, two ancestor buffers, the tree (parent, token, score per slot), the finished lists and the counter of
+    finished sentences.  Step 0's rows: row b * beam of every sentence is live, holds `bos`, slot b * beam, length 1."""
+
+    def __init__(self, B, beam, max_len, bos, device):
+        i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=device)  # noqa: E731
+        self.B, self.beam, self.max_len = int(B), int(beam), int(max_len)
+        R = self.B * self.beam
+        self.tree_slots = (self.max_len + 2) * R
+        self.cum = torch.zeros(R, dtype=torch.float32, device=device)
+        self.n_live = torch.ones(self.B, dtype=torch.int32, device=device)
+        first = torch.arange(R, device=device) % self.beam == 0
+        self.tokens = torch.where(first, int(bos), 0).to(torch.int32)
+        self.lengths = first.to(torch.int32)
+        self.slots = torch.arange(R, dtype=torch.int32, device=device)
+        self.ld_anc = self.max_len + 1
+        self.anc = [i32(R, self.ld_anc), i32(R, self.ld_anc)]
+        self.tree_parent = torch.full((self.tree_slots,), -1, dtype=torch.int32, device=device)
+        self.tree_token = i32(self.tree_slots)
+        self.tree_token[:R] = int(bos)
+        self.tree_score = torch.zeros(self.tree_slots, dtype=torch.float32, device=device)
+        self.fin_f = torch.zeros((self.B, self.beam, 3), dtype=torch.float32, device=device)
+        self.fin_i = i32(self.B, self.beam, 2)
+        self.n_fin = i32(self.B)
+        self.finished = i32(1)
+        self.ws = torch.zeros(int(_lib.lib().wavlm_beam_step_workspace_bytes(self.B, self.beam)), dtype=torch.uint8, device=device)
+        self.step = 0
+
+    def candidates(self):
+        """the last step's candidates: (scores fp32 [B, 2 beam], flat indices int32 [B, 2 beam], counts int32 [B])"""
+        n = self.B * 2 * self.beam
+        return (self.ws[:4 * n].view(torch.float32).view(self.B, -1), self.ws[4 * n:8 * n].view(torch.int32).view(self.B, -1),
+                self.ws[8 * n:8 * n + 4 * self.B].view(torch.int32))
+
+
+def beam_step(logits, st, V, *, max_len, min_len, pad, unk, eos, unk_penalty=0.0, temperature=1.0, len_penalty=1.0,
+              normalize_scores=True, step=None):
+    """one search step over st (a BeamState): logits [B * beam, >= V] of this step's rows (fp32 or bf16, unit column stride);
+    reads st.anc[step % 2], writes st.anc[(step + 1) % 2]; st.step goes up by one"""
+    _dev(logits)
+    step = st.step if step is None else int(step)
+    if logits.dim() != 2 or logits.shape[0] != st.B * st.beam or logits.shape[1] < V or logits.stride(1) != 1:
+        raise ValueError("logits must be [%d, >= %d] with unit column stride" % (st.B * st.beam, V))
+    if step > st.max_len:
+        raise ValueError("step %d is beyond the %d steps the state was made for" % (step, st.max_len))
+    L = _lib.lib()
+    check(L.wavlm_beam_step(ptr(logits), logits.stride(0), dt(logits), ptr(st.cum), ptr(st.n_live), ptr(st.tokens), ptr(st.lengths),
+                            ptr(st.slots), ptr(st.anc[step % 2]), ptr(st.anc[(step + 1) % 2]), st.ld_anc, ptr(st.tree_parent),
+                            ptr(st.tree_token), ptr(st.tree_score), st.tree_slots, ptr(st.fin_f), ptr(st.fin_i), ptr(st.n_fin),
+                            ptr(st.finished), st.B, st.beam, int(V), step, int(max_len), int(min_len), int(pad), int(unk), int(eos),
+                            float(unk_penalty), float(temperature), float(len_penalty), int(bool(normalize_scores)), ptr(st.ws),
+                            st.ws.numel(), stream()),
+          "wavlm_beam_step[B=%d beam=%d V=%d step=%d]" % (st.B, st.beam, V, step))
+    st.step = step + 1
+
+
 # ---------------------------------------------------------------------------------------------- CTC
 def _ctc_view(logits):
     """(stride_b, stride_t) in elements of a [B, T, C]-indexed view with unit class stride"""
