@@ -1009,6 +1009,25 @@ int wavlm_attn_step(const void* qkv, int64_t ld_qkv, void* Kc, void* Vc, int64_t
  *                         dtypes.  Returns -1 before the launch otherwise, and for a NULL pointer, anc_in == anc_out, ld_logits <
  *                         V, ld_anc < step + 1, tree_slots < (step + 2) B beam, temperature <= 0, a negative step or max_len, or
  *                         a short or misaligned workspace.
+ *   wavlm_beam_step_fused the same step -- same state arrays, tie rule, walk, finished lists, tree and workspace -- with two
+ *                         more rules.  Shallow fusion (338-344): lm_logits [B * beam, V] (lm_dtype, row stride ld_lm; NULL:
+ *                         none) gets a log-softmax of its own, without temperature, and per entry, in fp32 and in this order,
+ *                           lp = (x / temperature - M) - logS;  lm = (y - Ml) - logSl;  lp += lm_weight * lm
+ *                         before NaN -> -inf (346) and the rules above.  Taken literally: 0 * -inf is NaN, hence -inf, and a
+ *                         NaN anywhere in an LM row kills that row.  The n-gram blocker (no_repeat_ngram_size = n > 0,
+ *                         388-389, ngram_repeat_block.py:96-143) comes after those rules: the history of row k is h[j] =
+ *                         tree_token[anc_in[k][j]] for j < step and h[step] = tokens[row] (h[0] is the bos); for every i in
+ *                         0 .. step + 1 - n with h[i .. i + n - 2] == h[step + 2 - n .. step], token h[i + n - 1] is -inf.
+ *                         n = 1 bans every token of the history, eos included.  A banned token still counts in the normaliser.
+ *                         THE LOGITS BUFFER IS CONSUMED: once both log-softmax states are taken the workgroup overwrites
+ *                         the banned entries of `logits` with -inf -- those entries of live rows and nothing else; with n = 0
+ *                         nothing is written.  About history x n reads per row, no LDS sized by beam x V or beam x history,
+ *                         no atomics besides *finished.  With lm_logits == NULL and n == 0 every output equals
+ *                         wavlm_beam_step's bit for bit.  Bitwise reproducible; a sentence's result depends neither on B nor
+ *                         on its place in the batch.  Returns -1 before the launch, the state untouched, for everything
+ *                         wavlm_beam_step refuses and for ld_lm < V, a misaligned lm_logits or one that overlaps logits, an
+ *                         lm_dtype that is neither, n < 0 and an lm_weight that is not finite.  The workspace is
+ *                         wavlm_beam_step_workspace_bytes.
  * ------------------------------------------------------------------------------------------ */
 int wavlm_attn_cross_fwd_supported(int32_t head_dim, int32_t dtype);
 int wavlm_attn_cross_fwd(const void* Q, int64_t ld_q, const void* KV, int64_t s_kv, int64_t ld_kv, const int32_t* src_lengths,
@@ -1022,6 +1041,15 @@ int wavlm_beam_step(const void* logits, int64_t ld_logits, int32_t dtype, float*
                     int32_t* n_fin, int32_t* finished, int32_t B, int32_t beam, int32_t V, int32_t step, int32_t max_len,
                     int32_t min_len, int32_t pad, int32_t unk, int32_t eos, float unk_penalty, float temperature,
                     float len_penalty, int32_t normalize_scores, void* workspace, uint64_t ws_bytes, void* stream);
+int wavlm_beam_step_fused_supported(int32_t beam, int32_t V, int32_t B, int32_t dtype, int32_t lm_dtype);
+int wavlm_beam_step_fused(void* logits, int64_t ld_logits, int32_t dtype, const void* lm_logits, int64_t ld_lm, int32_t lm_dtype,
+                          float lm_weight, int32_t no_repeat_ngram_size, float* cum, int32_t* n_live, int32_t* tokens,
+                          int32_t* lengths, int32_t* slots, const int32_t* anc_in, int32_t* anc_out, int64_t ld_anc,
+                          int32_t* tree_parent, int32_t* tree_token, float* tree_score, int64_t tree_slots, float* fin_f,
+                          int32_t* fin_i, int32_t* n_fin, int32_t* finished, int32_t B, int32_t beam, int32_t V, int32_t step,
+                          int32_t max_len, int32_t min_len, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                          float temperature, float len_penalty, int32_t normalize_scores, void* workspace, uint64_t ws_bytes,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): HIP events around every wavlm_gemm launch while enabled.

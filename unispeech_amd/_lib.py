@@ -256,6 +256,10 @@ SIGNATURES = {
     "wavlm_beam_step": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp,
                                 c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32,
                                 c_f32, c_i32, c_vp, c_u64, c_vp]),
+    "wavlm_beam_step_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "wavlm_beam_step_fused": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                      c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp, c_u64, c_vp]),
     "wavlm_dp_set_listener": (None, [c_vp, c_vp]),
     "wavlm_dp_unique_id": (c_i32, [c_vp]),
     "wavlm_dp_init": (c_i32, [c_i32, c_i32, c_vp, c_i32]),

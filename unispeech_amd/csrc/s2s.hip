@@ -22,6 +22,13 @@
 //                          entry per lane, sorted, and the four lists are merged in wave order -- and the walk over them:
 //                          eos among the first `beam` ranks into the finished list, the first `beam` others into the next
 //                          step's rows.  Hypotheses are a tree of slots (parent, token, step score); nothing is reordered.
+//   wavlm_beam_step_fused  the same step with shallow fusion of a language model's logits (a second log-softmax state per row,
+//                          lp += lm_weight * lm before the NaN rule, sequence_generator.py:338-346) and the n-gram blocker
+//                          (ngram_repeat_block.py:96-143): after the log-softmax states are taken from the untouched logits, the
+//                          workgroup reads every row's history out of the tree (position i of row k to one thread: about
+//                          history x n reads per row, nothing of it in LDS) and overwrites the banned entries of the model's
+//                          logits with -inf; the scan behind the barrier reads -inf.  The logits buffer is consumed.  One
+//                          kernel template: without LM and blocker every float operation is wavlm_beam_step's.
 #include "common.hpp"
 #include "tile_loaders.hpp"
 #include "../../include/wavlm_hip.h"
@@ -369,8 +376,14 @@ __device__ __forceinline__ void bs_offer(float& ls, int& li, float s, int idx, b
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(BS_NT) void beam_step_kernel(const T* __restrict__ logits, int64_t ld_logits, float* __restrict__ cum,
+// the logits argument: read-only in wavlm_beam_step, written between two barriers by the blocker of the fused step
+template <typename T, bool FUSED> struct BsLogits { typedef const T* __restrict__ type; };
+template <typename T> struct BsLogits<T, true> { typedef T* type; };
+
+template <typename T, typename TL, bool FUSED>
+__global__ __launch_bounds__(BS_NT) void beam_step_kernel(typename BsLogits<T, FUSED>::type logits, int64_t ld_logits,
+                                                          const TL* __restrict__ lm, int64_t ld_lm, float lm_weight, int ngram,
+                                                          int tree_lim, float* __restrict__ cum,
                                                           int* __restrict__ n_live, int* __restrict__ tokens,
                                                           int* __restrict__ lengths, int* __restrict__ slots,
                                                           const int* __restrict__ anc_in, int* __restrict__ anc_out,
@@ -382,6 +395,7 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(const T* __restrict__ 
                                                           int* __restrict__ n_cand, int B, int beam, int V, int step, int max_len,
                                                           int min_len, int pad, int unk, int eos, float unk_penalty,
                                                           float temperature, float len_penalty, int normalize) {
+  __shared__ float lm_max[FUSED ? BS_MAXBEAM : 1], lm_logsum[FUSED ? BS_MAXBEAM : 1];
   __shared__ float row_max[BS_MAXBEAM], row_logsum[BS_MAXBEAM], row_cum[BS_MAXBEAM];
   __shared__ float ws_s[4][64];
   __shared__ int ws_i[4][64];
@@ -411,8 +425,50 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(const T* __restrict__ 
     const float M = wave_max(m);
     const float S = wave_sum(s * expf(m - M));     // a row of -inf alone: NaN, and every entry becomes -inf below
     if (lane == 0) { row_max[k] = M; row_logsum[k] = logf(S); row_cum[k] = cum[row0 + k]; }
+    if constexpr (FUSED) {
+      if (lm) {                                    // the LM's row the same way; it takes no temperature
+        const TL* lrow = lm + (row0 + k) * ld_lm;
+        float ml = -INFINITY, sl = 0.f;
+        for (int v = lane; v < V; v += 64) {
+          const float y = Elem<TL>::ld(lrow + v);
+          if (y == -INFINITY) continue;
+          const float mn = fmaxf(ml, y);
+          sl = sl * expf(ml - mn) + expf(y - mn);
+          ml = mn;
+        }
+        const float Ml = wave_max(ml);
+        const float Sl = wave_sum(sl * expf(ml - Ml));
+        if (lane == 0) { lm_max[k] = Ml; lm_logsum[k] = logf(Sl); }
+      }
+    }
   }
   __syncthreads();
+  if constexpr (FUSED) {
+    // the blocker (ngram_repeat_block.py:96-143): h[j] = tree_token[anc_in[k][j]] for j < step, h[step] = tokens[row].  For
+    // every i < cnt = step + 2 - ngram with h[i .. i + ngram - 2] == h[cnt .. step], token h[i + ngram - 1] is banned: its
+    // logit becomes -inf now that both log-softmax states are taken (a banned token still counts in the normaliser), and
+    // -inf stays -inf through every rule of the scan.  Several threads may write the same entry; they write the same value.
+    const int cnt = step + 2 - ngram;
+    if (ngram > 0 && cnt > 0) {                    // uniform over the workgroup
+      for (int e = tid; e < n * cnt; e += BS_NT) {
+        const int k = e / cnt, i = e - k * cnt;
+        const int* anc = anc_in + (row0 + k) * ld_anc;
+        const int last = tokens[row0 + k];
+        auto hist = [&](int j) -> int {
+          if (j >= step) return last;
+          const int sl = anc[j];
+          return (unsigned)sl < (unsigned)tree_lim ? tree_token[sl] : -1;
+        };
+        bool eq = true;
+        for (int j = 0; j < ngram - 1 && eq; ++j) eq = hist(i + j) == hist(cnt + j);
+        if (eq) {
+          const int t = hist(i + ngram - 1);
+          if ((unsigned)t < (unsigned)V) Elem<T>::st(logits + (row0 + k) * ld_logits + t, -INFINITY);
+        }
+      }
+      __syncthreads();
+    }
+  }
   const int total = n * V;
   const int K2 = 2 * beam < total - 1 ? 2 * beam : total - 1;     // search.py:131-135; >= 1 since V >= 2
   float ls = -INFINITY;
@@ -425,6 +481,14 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(const T* __restrict__ 
       const int k = idx / V, v = idx - k * V;
       const float x = Elem<T>::ld(logits + (row0 + k) * ld_logits + v) / temperature;
       float lp = (x - row_max[k]) - row_logsum[k];
+      if constexpr (FUSED) {
+        if (lm) {                                                  // 338-344: 0 * -inf is NaN, and a NaN is -inf below
+#pragma clang fp contract(off)
+          const float l = (Elem<TL>::ld(lm + (row0 + k) * ld_lm + v) - lm_max[k]) - lm_logsum[k];
+          const float wl = lm_weight * l;
+          lp = lp + wl;
+        }
+      }
       if (lp != lp) lp = -INFINITY;                                // sequence_generator.py:346
       if (v == pad) lp = -INFINITY;                                // 348
       if (v == unk) lp -= unk_penalty;                             // 349
@@ -578,11 +642,60 @@ int wavlm_beam_step(const void* logits, int64_t ld_logits, int32_t dtype, float*
   int* n_cand = cand_i + (int64_t)B * 2 * beam;
   hipStream_t st = (hipStream_t)stream;
 #define BS_GO(T)                                                                                                              \
-  WL_LAUNCH((beam_step_kernel<T>), dim3((unsigned)B), dim3(BS_NT), 0, st, (const T*)logits, ld_logits, cum, n_live, tokens,   \
+  WL_LAUNCH((beam_step_kernel<T, float, false>), dim3((unsigned)B), dim3(BS_NT), 0, st, (const T*)logits, ld_logits,          \
+            (const float*)nullptr, (int64_t)0, 0.f, 0, 0, cum, n_live, tokens,                                                \
             lengths, slots, anc_in, anc_out, ld_anc, tree_parent, tree_token, tree_score, fin_f, fin_i, n_fin, finished,      \
             cand_s, cand_i, n_cand, (int)B, (int)beam, (int)V, (int)step, (int)max_len, (int)min_len, (int)pad, (int)unk,     \
             (int)eos, unk_penalty, temperature, len_penalty, (int)normalize_scores)
   if (dtype == WL_BF16) BS_GO(bf16_t); else BS_GO(float);
+#undef BS_GO
+  return wl_check_launch();
+}
+
+int wavlm_beam_step_fused_supported(int32_t beam, int32_t V, int32_t B, int32_t dtype, int32_t lm_dtype) {
+  return wavlm_beam_step_supported(beam, V, B, dtype) && s2s_dt_ok(lm_dtype) ? 1 : 0;
+}
+
+int wavlm_beam_step_fused(void* logits, int64_t ld_logits, int32_t dtype, const void* lm_logits, int64_t ld_lm, int32_t lm_dtype,
+                          float lm_weight, int32_t no_repeat_ngram_size, float* cum, int32_t* n_live, int32_t* tokens,
+                          int32_t* lengths, int32_t* slots, const int32_t* anc_in, int32_t* anc_out, int64_t ld_anc,
+                          int32_t* tree_parent, int32_t* tree_token, float* tree_score, int64_t tree_slots, float* fin_f,
+                          int32_t* fin_i, int32_t* n_fin, int32_t* finished, int32_t B, int32_t beam, int32_t V, int32_t step,
+                          int32_t max_len, int32_t min_len, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                          float temperature, float len_penalty, int32_t normalize_scores, void* workspace, uint64_t ws_bytes,
+                          void* stream) {
+  if (!logits || !cum || !n_live || !tokens || !lengths || !slots || !anc_in || !anc_out || anc_in == anc_out || !tree_parent ||
+      !tree_token || !tree_score || !fin_f || !fin_i || !n_fin || !finished || !workspace ||
+      !wavlm_beam_step_fused_supported(beam, V, B, dtype, lm_logits ? lm_dtype : WL_F32))
+    return WL_EINVAL;
+  if (step < 0 || max_len < 0 || ld_logits < V || ld_anc < (int64_t)step + 1 || !(temperature > 0.f) ||
+      tree_slots < ((int64_t)step + 2) * B * beam || ((int64_t)step + 2) * B * beam > 0x7fffffffll ||
+      ws_bytes < wavlm_beam_step_workspace_bytes(B, beam) || ((uintptr_t)workspace & 15))
+    return WL_EINVAL;
+  if (((uintptr_t)logits & 3) || (dtype == WL_BF16 && ((uintptr_t)logits & 1))) return WL_EINVAL;
+  if (no_repeat_ngram_size < 0 || !isfinite(lm_weight)) return WL_EINVAL;
+  if (lm_logits) {
+    if (ld_lm < V || ((uintptr_t)lm_logits & (lm_dtype == WL_BF16 ? 1 : 3))) return WL_EINVAL;
+    // the blocker writes into `logits`: the two must not overlap
+    const uintptr_t a = (uintptr_t)logits, c = (uintptr_t)lm_logits;
+    const uint64_t na = (uint64_t)(((int64_t)B * beam - 1) * ld_logits + V) * (uint64_t)wl_esize(dtype);
+    const uint64_t nc = (uint64_t)(((int64_t)B * beam - 1) * ld_lm + V) * (uint64_t)wl_esize(lm_dtype);
+    if (a < c + nc && c < a + na) return WL_EINVAL;
+  }
+  float* cand_s = (float*)workspace;
+  int* cand_i = (int*)(cand_s + (int64_t)B * 2 * beam);
+  int* n_cand = cand_i + (int64_t)B * 2 * beam;
+  const int tree_lim = (int)(tree_slots < 0x7fffffffll ? tree_slots : 0x7fffffffll);
+  hipStream_t st = (hipStream_t)stream;
+#define BS_GO(T, TL)                                                                                                          \
+  WL_LAUNCH((beam_step_kernel<T, TL, true>), dim3((unsigned)B), dim3(BS_NT), 0, st, (T*)logits, ld_logits,                    \
+            (const TL*)lm_logits, ld_lm, lm_weight, (int)no_repeat_ngram_size, tree_lim, cum, n_live, tokens,                 \
+            lengths, slots, anc_in, anc_out, ld_anc, tree_parent, tree_token, tree_score, fin_f, fin_i, n_fin, finished,      \
+            cand_s, cand_i, n_cand, (int)B, (int)beam, (int)V, (int)step, (int)max_len, (int)min_len, (int)pad, (int)unk,     \
+            (int)eos, unk_penalty, temperature, len_penalty, (int)normalize_scores)
+  const bool lb = lm_logits && lm_dtype == WL_BF16;
+  if (dtype == WL_BF16) { if (lb) BS_GO(bf16_t, bf16_t); else BS_GO(bf16_t, float); }
+  else { if (lb) BS_GO(float, bf16_t); else BS_GO(float, float); }
 #undef BS_GO
   return wl_check_launch();
 }

@@ -1162,6 +1162,42 @@ def beam_step(logits, st, V, *, max_len, min_len, pad, unk, eos, unk_penalty=0.0
     st.step = step + 1
 
 
+def beam_step_fused_supported(beam, V, B, dtype, lm_dtype=torch.float32):
+    c = lambda d: BF16 if d == torch.bfloat16 else F32  # noqa: E731
+    return bool(_lib.lib().wavlm_beam_step_fused_supported(int(beam), int(V), int(B), c(dtype), c(lm_dtype)))
+
+
+def beam_step_fused(logits, st, V, *, max_len, min_len, pad, unk, eos, lm_logits=None, lm_weight=1.0, no_repeat_ngram_size=0,
+                    unk_penalty=0.0, temperature=1.0, len_penalty=1.0, normalize_scores=True, step=None):
+    """beam_step with shallow fusion and the n-gram blocker: lm_logits [B * beam, >= V] (fp32 or bf16, unit column stride; None:
+    no LM) enters as lm_weight * log_softmax(lm_logits) before the NaN rule; no_repeat_ngram_size = n > 0 bans, per row, every
+    token that would repeat an n-gram of the row's history (read from st's tree).  `logits` IS CONSUMED: with n > 0 the banned
+    entries of the live rows are overwritten with -inf (nothing else is written; with n = 0 nothing is).  With lm_logits None
+    and n = 0 the state after the call equals beam_step's bit for bit."""
+    _dev(logits)
+    step = st.step if step is None else int(step)
+    R = st.B * st.beam
+    if logits.dim() != 2 or logits.shape[0] != R or logits.shape[1] < V or logits.stride(1) != 1:
+        raise ValueError("logits must be [%d, >= %d] with unit column stride" % (R, V))
+    if lm_logits is not None and (lm_logits.dim() != 2 or lm_logits.shape[0] != R or lm_logits.shape[1] < V or
+                                  lm_logits.stride(1) != 1 or lm_logits.device != logits.device):
+        raise ValueError("lm_logits must be [%d, >= %d] with unit column stride on the device of logits" % (R, V))
+    if step > st.max_len:
+        raise ValueError("step %d is beyond the %d steps the state was made for" % (step, st.max_len))
+    L = _lib.lib()
+    check(L.wavlm_beam_step_fused(ptr(logits), logits.stride(0), dt(logits), ptr(lm_logits),
+                                  lm_logits.stride(0) if lm_logits is not None else 0,
+                                  dt(lm_logits) if lm_logits is not None else F32, float(lm_weight), int(no_repeat_ngram_size),
+                                  ptr(st.cum), ptr(st.n_live), ptr(st.tokens), ptr(st.lengths), ptr(st.slots), ptr(st.anc[step % 2]),
+                                  ptr(st.anc[(step + 1) % 2]), st.ld_anc, ptr(st.tree_parent), ptr(st.tree_token),
+                                  ptr(st.tree_score), st.tree_slots, ptr(st.fin_f), ptr(st.fin_i), ptr(st.n_fin), ptr(st.finished),
+                                  st.B, st.beam, int(V), step, int(max_len), int(min_len), int(pad), int(unk), int(eos),
+                                  float(unk_penalty), float(temperature), float(len_penalty), int(bool(normalize_scores)),
+                                  ptr(st.ws), st.ws.numel(), stream()),
+          "wavlm_beam_step_fused[B=%d beam=%d V=%d step=%d n=%d]" % (st.B, st.beam, V, step, int(no_repeat_ngram_size)))
+    st.step = step + 1
+
+
 # ---------------------------------------------------------------------------------------------- CTC
 def _ctc_view(logits):
     """(stride_b, stride_t) in elements of a [B, T, C]-indexed view with unit class stride"""

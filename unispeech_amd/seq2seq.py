@@ -24,13 +24,22 @@ encoder's frames) decoded the way `SequenceGenerator` (src/fairseq/sequence_gene
                      wavlm_beam_step.  The shapes are the same at every step; finished sentences' rows are skipped through
                      `lengths`.  Inside the loop the host reads one int32 -- the count of finished sentences -- every
                      READ_EVERY steps (read_device counts the reads: Wav2Vec2Seq2Seq.loop_reads).
-                     Refused by name: prefix_tokens, constraints, sampling, match_source_len, no_repeat_ngram_size, ensembles,
-                     lm_model.
+                     Refused by name: prefix_tokens, constraints, sampling, match_source_len, ensembles -- and lm_model,
+                     lm_weight and no_repeat_ngram_size, which sequence_generator.SequenceGenerator takes.
+  search             generate() behind the encoder.  Keyword-only lm_model= (a TransformerLM over the same dictionary), lm_weight=
+                     and no_repeat_ngram_size= turn the step into wavlm_beam_step_fused: the LM runs incrementally over caches
+                     of its own shaped as the same tree (wavlm_attn_step with the search's slots, ancestors and lengths), one
+                     wavlm_gemm gives its logits, and the step adds lm_weight * log_softmax before the NaN rule
+                     (sequence_generator.py:338-346; a plain log-softmax: FairseqLM's unk rule is not SequenceGenerator's) and
+                     bans repeated n-grams from the tree's histories (ngram_repeat_block.py).  No host read is added.  Taken
+                     literally: lm_weight 0 against an LM entry of -inf is NaN, hence -inf; no_repeat_ngram_size 1 bans
+                     every token of the history, eos (the row's first token) included.
   decoder_reference, beam_step_reference, beam_search_reference, generate_reference
                      the same in float64 torch on the CPU: the specification.  Host tensors go through these; there is no CPU
                      build of the kernels.
   python -m unispeech_amd.seq2seq decode CKPT DICT audio.wav ... [--beam N --max-len-a A --max-len-b B --lenpen P --nbest N]
   python -m unispeech_amd.seq2seq score CKPT DICT MANIFEST.tsv LABELS.ltr [--results DIR]
+      either with [--lm LM.pt --lm-weight W] [--no-repeat-ngram-size N]: LM.pt is a TransformerLM checkpoint over the same DICT
 
 Ties: candidates are ordered by (score descending, beam row * V + token ascending).  torch.topk leaves ties open.
 bf16 and fp32 (parity) modes: `.to(torch.bfloat16)` as the other heads have it; the search itself is fp32 in both.
@@ -46,11 +55,12 @@ import torch.nn as nn
 from .transformer_lm import _attend64, _lin64, _ln64, sinusoidal_table
 
 __all__ = ["Seq2SeqConfig", "Wav2Vec2Seq2Seq", "decoder_reference", "beam_step_reference", "beam_search_reference",
-           "generate_reference", "read_device"]
+           "generate_reference", "ngram_banned", "read_device"]
 
 READ_EVERY = 8                         # steps between two reads of the finished counter
 GENERATE_REFUSED = ("prefix_tokens", "constraints", "sampling", "sampling_topk", "sampling_topp", "match_source_len",
                     "no_repeat_ngram_size", "lm_model", "lm_weight", "diverse_beam_groups", "diversity_rate", "models", "ensemble")
+FUSION_OPTIONS = ("lm_model", "lm_weight", "no_repeat_ngram_size")     # built, behind sequence_generator.SequenceGenerator
 
 
 class Seq2SeqConfig:
@@ -420,6 +430,9 @@ class Wav2Vec2Seq2Seq(nn.Module):
         for k, v in refused.items():
             if k in GENERATE_REFUSED:
                 if v is not None and v is not False and not (isinstance(v, (int, float)) and v == 0):
+                    if k in FUSION_OPTIONS:
+                        raise NotImplementedError("%s is not an option of generate: unispeech_amd.sequence_generator."
+                                                  "SequenceGenerator takes it" % k)
                     raise NotImplementedError("%s is not built (see unispeech_amd/seq2seq.py)" % k)
             else:
                 raise TypeError("generate: unknown option %r" % k)
@@ -431,17 +444,55 @@ class Wav2Vec2Seq2Seq(nn.Module):
                             step_logits)
 
     def search(self, enc, src_len, beam=5, max_len_a=0, max_len_b=200, min_len=1, normalize_scores=True, len_penalty=1.0,
-               unk_penalty=0.0, temperature=1.0, nbest=None, step_logits=None):
-        """generate() behind the encoder: enc is what attend_to returned, src_len the padded source length max_len is taken from"""
-        max_len = self._search_limits(enc[0].shape[0], src_len, beam, max_len_a, max_len_b, min_len)
-        return self._search(enc, max_len, beam, min_len, normalize_scores, len_penalty, unk_penalty, temperature, nbest,
-                            step_logits)
+               unk_penalty=0.0, temperature=1.0, nbest=None, step_logits=None, *, max_len=None, lm_model=None, lm_weight=1.0,
+               no_repeat_ngram_size=0):
+        """generate() behind the encoder: enc is what attend_to returned, src_len the padded source length max_len is taken from
+        (max_len: an upper limit of its own on top, SequenceGenerator's).  lm_model (a TransformerLM over the same dictionary),
+        lm_weight: shallow fusion; no_repeat_ngram_size: the n-gram blocker (unispeech_amd/sequence_generator.py is the public
+        entry to both)."""
+        limit = self._search_limits(enc[0].shape[0], src_len, beam, max_len_a, max_len_b, min_len)
+        if max_len is not None:
+            limit = min(limit, int(max_len))
+            if min_len > limit:
+                raise ValueError("min_len cannot be larger than max_len (%d, %d)" % (min_len, limit))
+        self._check_fusion(lm_model, lm_weight, no_repeat_ngram_size, limit, enc[2][0].device)
+        return self._search(enc, limit, beam, min_len, normalize_scores, len_penalty, unk_penalty, temperature, nbest,
+                            step_logits, lm_model=lm_model, lm_weight=lm_weight, no_repeat_ngram_size=no_repeat_ngram_size)
 
-    def _search(self, enc, max_len, beam, min_len, normalize_scores, len_penalty, unk_penalty, temperature, nbest, step_logits):
+    def _check_fusion(self, lm_model, lm_weight, no_repeat_ngram_size, max_len, device):
+        """what the fused search refuses, before anything runs"""
+        from .transformer_lm import TransformerLM
+        if int(no_repeat_ngram_size) < 0:
+            raise ValueError("no_repeat_ngram_size must be >= 0, got %r" % (no_repeat_ngram_size,))
+        if lm_model is None:
+            return
+        if not isinstance(lm_model, TransformerLM):
+            raise NotImplementedError("lm_model must be a unispeech_amd.transformer_lm.TransformerLM, got %s"
+                                      % type(lm_model).__name__)
+        if not math.isfinite(float(lm_weight)):
+            raise ValueError("lm_weight must be finite, got %r" % (lm_weight,))
+        mine, theirs = (self.vocab, self.pad, self.eos, self.unk), (lm_model.vocab, lm_model.pad, lm_model.eos, lm_model.unk)
+        if mine != theirs:
+            raise ValueError("lm_model's dictionary (vocab, pad, eos, unk) = %r differs from the model's %r" % (theirs, mine))
+        lm_dev = lm_model.decoder.output_projection.weight.device
+        if lm_dev != torch.device(device):
+            raise ValueError("lm_model is on %s, the model on %s" % (lm_dev, device))
+        lc = lm_model.cfg
+        if lc.decoder_learned_pos and not lc.no_token_positional_embeddings and max_len + 1 > lc.max_target_positions:
+            raise ValueError("max_len + 1 = %d target positions are more than max_target_positions = %d of lm_model's learned "
+                             "positions" % (max_len + 1, lc.max_target_positions))
+        hd = lc.decoder_embed_dim // lc.decoder_attention_heads
+        if hd * lc.decoder_attention_heads != lc.decoder_embed_dim or hd not in (32, 64):
+            raise NotImplementedError("lm_model: wavlm_attn_step takes heads 32 or 64 wide, not %d / %d"
+                                      % (lc.decoder_embed_dim, lc.decoder_attention_heads))
+
+    def _search(self, enc, max_len, beam, min_len, normalize_scores, len_penalty, unk_penalty, temperature, nbest, step_logits,
+                *, lm_model=None, lm_weight=1.0, no_repeat_ngram_size=0):
         from . import ops
         B, V = enc[0].shape[0], self.vocab
         cfg = self.cfg
         H, D, L = cfg.decoder_attention_heads, cfg.decoder_embed_dim, cfg.decoder_layers
+        fused = lm_model is not None or int(no_repeat_ngram_size) > 0
         with torch.no_grad():
             _, src_lengths, kv = enc
             dev, dtype = kv[0].device, kv[0].dtype
@@ -452,6 +503,12 @@ class Wav2Vec2Seq2Seq(nn.Module):
             vc = [torch.zeros((slots, D), dtype=dtype, device=dev) for _ in range(L)]
             offsets = (torch.arange(B + 1, dtype=torch.int32, device=dev) * beam).contiguous()
             self._positions(self._images(), max_len + 1)
+            if lm_model is not None:                                  # the LM's own caches over the same tree of slots
+                lc = lm_model.cfg
+                H_lm, lm_w = lc.decoder_attention_heads, lm_model.decoder.output_projection.weight
+                lm_kc = [torch.zeros((slots, lc.decoder_embed_dim), dtype=lm_w.dtype, device=dev) for _ in range(lc.decoder_layers)]
+                lm_vc = [torch.zeros((slots, lc.decoder_embed_dim), dtype=lm_w.dtype, device=dev) for _ in range(lc.decoder_layers)]
+                lm_model._positions(lm_model._images(), max_len + 1)
             self.loop_reads = self.loop_steps = 0
             for step in range(max_len + 1):
                 self.loop_steps = step + 1
@@ -461,11 +518,28 @@ class Wav2Vec2Seq2Seq(nn.Module):
                                 lambda i, qkv: ops.attn_step(qkv, kc[i], vc[i], st.slots, anc, lengths, H, step + 1),
                                 lambda i, q: ops.attn_cross_fwd(q, kv[i], H, offsets, src_lengths, live=lengths, max_group=beam))
                 logits = self._logits(x)
-                if step_logits is not None:
-                    step_logits.append((logits.clone(), lengths.clone()))
-                ops.beam_step(logits, st, V, max_len=max_len, min_len=min_len, pad=self.pad, unk=self.unk, eos=self.eos,
-                              unk_penalty=unk_penalty, temperature=temperature, len_penalty=len_penalty,
-                              normalize_scores=normalize_scores, step=step)
+                if fused:
+                    lm_logits = None
+                    if lm_model is not None:                          # a plain log-softmax scores it: no unk rule here
+                        y = lm_model._stack(st.tokens, pidx, step + 1,
+                                            lambda i, qkv: ops.attn_step(qkv, lm_kc[i], lm_vc[i], st.slots, anc, lengths, H_lm,
+                                                                         step + 1))
+                        ld = (V + 3) // 4 * 4
+                        lm_logits = torch.empty((R, ld), dtype=torch.float32, device=dev)
+                        ops.gemm(y, lm_w, lm_logits, R, V, y.shape[1], lda=y.stride(0), ldb=lm_w.stride(0), ldc=ld)
+                        lm_logits = lm_logits[:, :V]
+                    if step_logits is not None:
+                        step_logits.append((logits.clone(), lengths.clone(), None if lm_logits is None else lm_logits.clone()))
+                    ops.beam_step_fused(logits, st, V, max_len=max_len, min_len=min_len, pad=self.pad, unk=self.unk, eos=self.eos,
+                                        lm_logits=lm_logits, lm_weight=lm_weight, no_repeat_ngram_size=no_repeat_ngram_size,
+                                        unk_penalty=unk_penalty, temperature=temperature, len_penalty=len_penalty,
+                                        normalize_scores=normalize_scores, step=step)
+                else:
+                    if step_logits is not None:
+                        step_logits.append((logits.clone(), lengths.clone()))
+                    ops.beam_step(logits, st, V, max_len=max_len, min_len=min_len, pad=self.pad, unk=self.unk, eos=self.eos,
+                                  unk_penalty=unk_penalty, temperature=temperature, len_penalty=len_penalty,
+                                  normalize_scores=normalize_scores, step=step)
                 if step % READ_EVERY == READ_EVERY - 1 and step < max_len:
                     self.loop_reads += 1
                     if int(read_device(st.finished)) >= B:
@@ -547,15 +621,22 @@ def decoder_reference(model, encoder_out, padding_mask, tokens):
 
 
 def beam_step_reference(logits, cum, step, n_fin, *, beam, max_len, min_len, pad, unk, eos, unk_penalty=0.0, temperature=1.0,
-                        len_penalty=1.0, normalize_scores=True, full=False):
+                        len_penalty=1.0, normalize_scores=True, full=False, lm_logits=None, lm_weight=1.0, history=None,
+                        no_repeat_ngram_size=0):
     """one sentence, one step, float64: logits [n_live, V] of its live rows, cum [n_live] their cumulative scores, n_fin the
     entries its finished list holds -> {"candidates": [(score, k * V + token)] in order, "finished": [(score, raw score, step
     score, parent row k, length)], "rows": [(parent row k, token, cumulative score, step score)], "done": bool}.  The rules of
-    sequence_generator.py:346-367 and 405-520 with search.py:119-136; ties go to the smaller k * V + token."""
+    sequence_generator.py:346-367 and 405-520 with search.py:119-136; ties go to the smaller k * V + token.
+    lm_logits [n_live, V]: lm_weight * log_softmax(lm_logits) is added before the NaN rule (338-346; 0 * -inf is NaN, hence
+    -inf).  no_repeat_ngram_size = n > 0 with history (per row its tokens h[0 .. step], h[0] the bos): after the other rules every
+    token that would repeat an n-gram of h is -inf (ngram_repeat_block.py:96-143, n = 1 included: every token of h);
+    "banned": the rows' sets of such tokens."""
     x = torch.as_tensor(logits, dtype=torch.float64) / temperature
     cum = torch.as_tensor(cum, dtype=torch.float64)
     n, V = x.shape
     lp = torch.log_softmax(x, -1)
+    if lm_logits is not None:
+        lp = lp + lm_weight * torch.log_softmax(torch.as_tensor(lm_logits, dtype=torch.float64), -1)
     lp[lp != lp] = -math.inf
     lp[:, pad] = -math.inf
     lp[:, unk] -= unk_penalty
@@ -564,6 +645,15 @@ def beam_step_reference(logits, cum, step, n_fin, *, beam, max_len, min_len, pad
         lp[:, eos + 1:] = -math.inf
     if step < min_len:
         lp[:, eos] = -math.inf
+    banned = None
+    if no_repeat_ngram_size > 0:
+        if history is None or len(history) != n:
+            raise ValueError("no_repeat_ngram_size needs the history of each of the %d rows" % n)
+        banned = [ngram_banned(h, step, no_repeat_ngram_size) for h in history]
+        for k, ban in enumerate(banned):
+            for t in ban:
+                if 0 <= t < V:
+                    lp[k, t] = -math.inf
     sc = (lp + cum.unsqueeze(1)).reshape(-1)
     sc[sc != sc] = -math.inf
     K2 = min(2 * beam, n * V - 1)
@@ -580,18 +670,35 @@ def beam_step_reference(logits, cum, step, n_fin, *, beam, max_len, min_len, pad
             rows.append((k, tok, s, s - float(cum[k])))
     done = n_fin + len(finished) >= beam or step >= max_len or not rows
     res = {"candidates": cands, "finished": finished, "rows": [] if done else rows, "done": done}
+    if banned is not None:
+        res["banned"] = banned
     if full:                                                          # every entry in order, and the rows before `done` cut them
         res["all"] = [(float(vals[i]), int(i)) for i in np.lexsort((np.arange(vals.size), -vals))]
         res["rows_taken"] = rows
     return res
 
 
+def ngram_banned(h, step, n):
+    """the tokens _no_repeat_ngram bans after the history h[0 .. step] (h[0] the bos): for every i in 0 .. step + 1 - n with
+    h[i .. i + n - 2] == h[step + 2 - n .. step], token h[i + n - 1].  The reference builds its n-grams over the whole padded
+    row; the further ones can only ban pad, which is -inf already."""
+    h = [int(t) for t in h]
+    if len(h) != step + 1:
+        raise ValueError("a history of %d tokens at step %d" % (len(h), step))
+    cnt = step + 2 - n
+    tail = h[cnt:] if cnt >= 0 else None
+    return {h[i + n - 1] for i in range(max(cnt, 0)) if h[i:i + n - 1] == tail}
+
+
 def beam_search_reference(step_logits_fn, B, *, bos, beam=5, max_len=200, min_len=1, pad=1, unk=3, eos=2, unk_penalty=0.0,
-                          temperature=1.0, len_penalty=1.0, normalize_scores=True, nbest=None, margins=None):
+                          temperature=1.0, len_penalty=1.0, normalize_scores=True, nbest=None, margins=None, lm_logits_fn=None,
+                          lm_weight=1.0, no_repeat_ngram_size=0):
     """SequenceGenerator._generate + BeamSearch.step + finalize_hypos restated in float64 on the host.
     step_logits_fn(b, prefixes) -> logits [len(prefixes), V] of the next token after each prefix (lists of ids that begin with
     bos) of sentence b.  -> per sentence the finished hypotheses sorted by score, each {"tokens", "score", "positional_scores"}.
-    margins (a list): receives, per sentence and step, the gap between the last candidate taken and the first one left out."""
+    margins (a list): receives, per sentence and step, the gap between the last candidate taken and the first one left out.
+    lm_logits_fn(b, prefixes) -> the LM's logits [len(prefixes), V] (None: no LM), weighed by lm_weight; no_repeat_ngram_size:
+    the blocker over the prefixes."""
     opts = dict(beam=beam, max_len=max_len, min_len=min_len, pad=pad, unk=unk, eos=eos, unk_penalty=unk_penalty,
                 temperature=temperature, len_penalty=len_penalty, normalize_scores=normalize_scores)
     out = []
@@ -599,9 +706,14 @@ def beam_search_reference(step_logits_fn, B, *, bos, beam=5, max_len=200, min_le
         prefixes, cum, pos, hyps = [[bos]], [0.0], [[]], []
         for step in range(max_len + 1):
             logits = torch.as_tensor(step_logits_fn(b, prefixes), dtype=torch.float64)
-            r = beam_step_reference(logits, cum, step, len(hyps), **opts)
+            extra = {}
+            if lm_logits_fn is not None:
+                extra.update(lm_logits=torch.as_tensor(lm_logits_fn(b, prefixes), dtype=torch.float64), lm_weight=lm_weight)
+            if no_repeat_ngram_size > 0:
+                extra.update(history=prefixes, no_repeat_ngram_size=no_repeat_ngram_size)
+            r = beam_step_reference(logits, cum, step, len(hyps), **opts, **extra)
             if margins is not None:
-                margins.append(_margin(logits, cum, step, r, opts))
+                margins.append(_margin(logits, cum, step, r, dict(opts, **extra)))
             for score, raw, ss, k, length in r["finished"]:
                 hyps.append({"tokens": torch.tensor(prefixes[k][1:] + [eos], dtype=torch.long),
                              "score": torch.tensor(score, dtype=torch.float64),
@@ -632,10 +744,19 @@ def _margin(logits, cum, step, r, opts):
     return min(gaps) if gaps else math.inf
 
 
-def generate_reference(model, encoder_out, padding_mask, src_len, beam=5, max_len_a=0, max_len_b=200, min_len=1, **kw):
+def generate_reference(model, encoder_out, padding_mask, src_len, beam=5, max_len_a=0, max_len_b=200, min_len=1, lm_model=None,
+                       **kw):
     """Wav2Vec2Seq2Seq.generate's result in float64 on the CPU from the encoder's output [B, Ts, D] (after proj): every step
-    re-runs decoder_reference over the whole prefix"""
+    re-runs decoder_reference over the whole prefix -- and, with lm_model (a TransformerLM; lm_weight=, and
+    no_repeat_ngram_size= likewise), transformer_lm._forward64 over it"""
     max_len = model._max_len(src_len, max_len_a, max_len_b)
+    if lm_model is not None:
+        from .transformer_lm import _forward64
+
+        def lm_fn(b, prefixes):
+            with torch.no_grad():
+                return torch.stack([_forward64(lm_model, p[1:])[-1] for p in prefixes])
+        kw["lm_logits_fn"] = lm_fn
 
     def fn(b, prefixes):
         tok = torch.tensor(prefixes, dtype=torch.long)
@@ -657,6 +778,9 @@ def parse_args(argv=None):
         q.add_argument("--max-len-b", type=int, default=200)
         q.add_argument("--lenpen", type=float, default=1.0)
         q.add_argument("--nbest", type=int, default=1)
+        q.add_argument("--lm", default=None, metavar="LM.pt", help="a TransformerLM checkpoint over the same DICT: shallow fusion")
+        q.add_argument("--lm-weight", type=float, default=1.0)
+        q.add_argument("--no-repeat-ngram-size", type=int, default=0, metavar="N", help="no n-gram occurs twice in a hypothesis")
     return p.parse_args(argv)
 
 
@@ -673,6 +797,22 @@ def _search_kwargs(a):
     return dict(beam=a.beam, max_len_a=a.max_len_a, max_len_b=a.max_len_b, len_penalty=a.lenpen, nbest=a.nbest)
 
 
+def _generator(a, d, model, nbest=None):
+    """source, padding_mask -> hypotheses: generate() itself, or SequenceGenerator where an LM or the blocker is asked for"""
+    kw = dict(_search_kwargs(a), nbest=a.nbest if nbest is None else nbest)
+    if a.lm is None and not a.no_repeat_ngram_size:
+        return lambda src, pm: model.generate(src, pm, **kw)
+    from .sequence_generator import SequenceGenerator
+    from .transformer_lm import TransformerLM
+    lm = None
+    if a.lm is not None:
+        lm = TransformerLM.from_checkpoint(a.lm, len(d), pad=d.pad(), eos=d.eos(), unk=d.unk()).cuda()
+        lm = lm.to(next(model.parameters()).dtype)
+    gen = SequenceGenerator([model], d, beam_size=a.beam, max_len_a=a.max_len_a, max_len_b=a.max_len_b, len_penalty=a.lenpen,
+                            no_repeat_ngram_size=a.no_repeat_ngram_size, lm_model=lm, lm_weight=a.lm_weight)
+    return lambda src, pm: [h[:kw["nbest"]] for h in gen.generate([model], {"net_input": {"source": src, "padding_mask": pm}})]
+
+
 def _strip(tokens, d):
     return [int(t) for t in tokens if int(t) not in (d.pad(), d.eos())]
 
@@ -681,6 +821,7 @@ def decode(a):
     from .ctc import post_process
     from .kmeans import read_wav
     d, model, dtype = _load(a)
+    run = _generator(a, d, model)
     symbol = None if a.post_process == "none" else "letter"
     for path in a.wavs:
         wav, sr = read_wav(path)
@@ -689,7 +830,7 @@ def decode(a):
         x = torch.as_tensor(wav, dtype=torch.float32).cuda()
         if getattr(model, "normalize", False):
             x = torch.nn.functional.layer_norm(x, x.shape)
-        for h in model.generate(x.view(1, -1).to(dtype), None, **_search_kwargs(a))[0]:
+        for h in run(x.view(1, -1).to(dtype), None)[0]:
             text = post_process(d.string(_strip(h["tokens"], d)), symbol)
             print(text if a.nbest == 1 else "%.4f\t%s" % (float(h["score"]), text))
     return 0
@@ -700,6 +841,7 @@ def score(a):
     from .ctc import edit_distance, length_batches, post_process, read_labels, read_manifest
     from .kmeans import read_wav
     d, model, dtype = _load(a)
+    run = _generator(a, d, model, nbest=1)
     symbol = None if a.post_process == "none" else "letter"
     entries = read_manifest(a.manifest)
     labels = read_labels(a.labels, d, len(entries))
@@ -720,7 +862,7 @@ def score(a):
         for r, w in enumerate(wavs):
             src[r, :w.numel()] = w
             pm[r, :w.numel()] = False
-        res = model.generate(src.cuda().to(dtype), pm.cuda() if bool(pm.any()) else None, **dict(_search_kwargs(a), nbest=1))
+        res = run(src.cuda().to(dtype), pm.cuda() if bool(pm.any()) else None)
         for r, i in enumerate(batch):
             pred = _strip(res[r][0]["tokens"], d) if res[r] else []
             targ = [v for v in labels[i] if v not in (d.pad(), d.eos())]
