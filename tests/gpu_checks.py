@@ -52,6 +52,29 @@ test_posconv_ref.py holds its CPU side.  The constants a retune would move: posc
                          nsplit 1 and 4, at (96, 48, 128) and (1024, 64, 128); PosConvFn's GEMM form at (B, T, D, G) = (2, 49, 64, 4)
                          with K = 15, 3 (odd: the left pad of the gradient copy is K - 1 - K // 2) and 16; the refusals
 Bounds: check_posconv's (tol_for(dtype) for y, x 2 for dx and dbias, x 3 for dv and dg; 1e-2 between the direct and the GEMM form).
+
+The fused attention (attn_fused.hip, attn_fused_dkv.hip; ops.attn_fused_fwd / attn_fused_bwd, F.AttnCoreFn) has three groups at its
+launch geometry, bf16 with head_dim 64, against _ref_attention / _ref_attention_masked in fp64 on the device; tests/
+test_attention_ref.py holds their CPU side.  The constants a retune would move: 128 query rows per block of the forward and dQ
+kernels and 128 key rows per block of the dK/dV kernel (FA_BQ), 4 partial rows per block -- one per wave of 32 rows -- for d(rel)
+and for the q|k|v bias gradient (FA_PART), so ntot = B x 4 x ceil(T / 128) partial rows; fa_dtab_reduce_kernel's 64 row slices x 4
+rows in flight, stepping by 256 (FA_RED_STRIDE): slice s adds the rows s + 64 u + 256 k; 64-key tiles of the online softmax;
+FA_PSTORE_MAX_T = 1024 = FA_DKVP_ROWS, the last T with a probability store:
+  attention_reduce       (B, H, T) = (17, 1, 100): ntot 68, the first use of u = 1; (33, 2, 130): 264, a second sweep with a ragged
+                         end, 8 rows per item; (11, 1, 700): 264 with 24 rows per item, so item and row-in-item change in the
+                         middle of a sweep; (32, 1, 749): 768, the training step's count.  Whole-batch parity of O, dqkv, dgate, dtab
+                         and dbias (fp32 and bf16, written into NaN-filled memory and added onto a base) in the recompute and
+                         stored-P modes; each of the partial rows 0, 63, 64, 65, 127, 128, 191, 192, 255, 256, ntot - 1 ALONE (dO zero
+                         elsewhere) against a B = 1 reference of its item, the other items' dqkv and dgate exactly zero; gate = tab =
+                         None at (33, 2, 130).  Every backward runs over a workspace of 0xFF bytes
+  attention_ragged       B = 8, H = 2, T = 300: lengths 300, 257, 256, 129, 65, 2; keys [0, 70) and [128, 192) masked (a dead first
+                         tile, a dead tile between live ones); length 1.  PER ITEM, each slice against its own reference maximum;
+                         recompute, stored P and unfused without dropout, the three fused modes with dropout 0.25 under the kernels'
+                         own mask (identical in forward, dQ, dK/dV); dk, dv of masked keys exactly zero; an item alone gives the bits
+                         it gives in the batch
+  attention_long         T = 1024 (store returned, LDS row arrays full), 1025 (no store: AttnCoreFn recomputes), (2, 2, 1153) with
+                         item 1 at 1030, 1537; dropout 0.25 at 1025 in the recompute and stored-bits modes, bit-identical
+Bounds: check_attention's (TOLBF for O, 2 x TOLBF for gradients), per slice where the metric is per item.
 """
 import math
 import sys
@@ -901,8 +924,8 @@ def _ref_attention(qkv, gate, tab, kpm, H, scale):
     vh = qkv[..., 2 * D:].view(B, T, H, hd).permute(0, 2, 1, 3)
     s = (qh @ kh.transpose(-1, -2)) * scale
     if tab is not None:
-        i = torch.arange(T)[:, None]
-        j = torch.arange(T)[None, :]
+        i = torch.arange(T, device=qkv.device)[:, None]   # (the reference runs where its inputs live: CPU or device)
+        j = torch.arange(T, device=qkv.device)[None, :]
         rel = tab[:, (j - i) + T - 1]  # [H, T, T]
         s = s + gate.unsqueeze(-1) * rel.unsqueeze(0)
     if kpm is not None:
@@ -1096,8 +1119,8 @@ def _ref_attention_masked(qkv, gate, tab, kpm, H, scale, keep, sc):
     vh = qkv[..., 2 * D:].view(B, T, H, hd).permute(0, 2, 1, 3)
     s = (qh @ kh.transpose(-1, -2)) * scale
     if tab is not None:
-        i = torch.arange(T)[:, None]
-        j = torch.arange(T)[None, :]
+        i = torch.arange(T, device=qkv.device)[:, None]   # (the reference runs where its inputs live: CPU or device)
+        j = torch.arange(T, device=qkv.device)[None, :]
         s = s + gate.unsqueeze(-1) * tab[:, (j - i) + T - 1].unsqueeze(0)
     if kpm is not None:
         s = s.masked_fill(kpm.bool()[:, None, None, :], float("-inf"))
@@ -3195,6 +3218,311 @@ def check_posconv_layouts():
     return out
 
 
+# ------------------------------------------------------------------------- fused attention at launch geometry
+FA_BQ = 128                # query rows per block of the forward and the dQ kernel = key rows per block of the dK/dV kernel (FA_BK1)
+FA_PART = 4                # partial rows per block (d(rel) and q|k|v bias gradient): one per wave of 32 rows
+FA_RED_STRIDE = 64 * 4     # fa_dtab_reduce_kernel: 64 row slices x 4 rows in flight (u = 0..3), then r0 += 256
+FA_PSTORE_MAX_T = 1024     # attn_fused.hpp: no probability store beyond; FA_DKVP_ROWS of the stored-P dK/dV kernel is the same number
+ATTN_SCALE = 64 ** -0.5
+ATTN_DROP = 0.25           # 16384 / 65536: exact in the kernels' 16-bit threshold, sc = 4 / 3
+ATTN_REDUCE_SHAPES = [(17, 1, 100), (33, 2, 130), (11, 1, 700), (32, 1, 749)]   # B, H, T: ntot = 68, 264, 264, 768 partial rows
+ATTN_REDUCE_PROBES = (0, 63, 64, 65, 127, 128, 191, 192, 255, 256)              # and ntot - 1: the u and sweep boundaries
+ATTN_RAGGED_LENGTHS = (300, 257, 256, 129, 65, 2)                               # items 0..5 of the ragged batch (T = 300)
+ATTN_LONG_CASES = [(1, 1, 1024, None), (1, 1, 1025, None), (2, 2, 1153, 1030), (1, 1, 1537, None)]   # B, H, T, length of item 1
+
+
+def fa_partial_rows(B, T):
+    nrow = FA_PART * ((T + FA_BQ - 1) // FA_BQ)
+    return nrow, B * nrow
+
+
+def fa_inputs(B, H, T, tabbed=True, seed=11, host=False):
+    """bf16 qkv and dO, fp32 gate and table on the device; host=True: check_attention's CPU draws of the same seeds"""
+    D = 64 * H
+    g = (lambda *s, seed: gen(*s, seed=seed).to(DEV)) if host else dgen
+    qkv = g(B, T, 3 * D, seed=seed).to(torch.bfloat16)
+    gate = 1 + 0.5 * g(B, H, T, seed=seed + 1) if tabbed else None
+    tab = 0.5 * g(H, 2 * T - 1, seed=seed + 2) if tabbed else None
+    dO = g(B, T, D, seed=seed + 3).to(torch.bfloat16)
+    return qkv, gate, tab, dO
+
+
+def fa_ref64(qkv, gate, tab, kpm, H, dO, keep=None, sc=1.0):
+    """_ref_attention (_ref_attention_masked with a keep mask) and its gradients in float64 where the inputs live; dbias = column
+    sums of dqkv over (b, t)"""
+    qr = qkv.double().requires_grad_(True)
+    gr = tr = None
+    if tab is not None:
+        gr, tr = gate.double().requires_grad_(True), tab.double().requires_grad_(True)
+    if keep is None:
+        Or = _ref_attention(qr, gr, tr, kpm, H, ATTN_SCALE)
+    else:
+        Or = _ref_attention_masked(qr, gr, tr, kpm, H, ATTN_SCALE, keep, sc)
+    g = torch.autograd.grad(Or, [qr] + ([gr, tr] if tab is not None else []), dO.double())
+    return {"O": Or.detach(), "dqkv": g[0], "dgate": g[1] if tab is not None else None, "dtab": g[2] if tab is not None else None,
+            "dbias": g[0].sum((0, 1))}
+
+
+def fa_hostile_workspace(dev, B, H, T):
+    """0xFF into every byte of the backward's workspace: each float the kernels do not write themselves reads as NaN"""
+    from unispeech_amd import _lib
+    need = int(_lib.lib().wavlm_attn_fused_bwd_workspace_bytes(B, H, T))
+    ops.workspace(dev, need, "attn").fill_(0xFF)
+
+
+def fa_device(qkv, gate, tab, kpm, H, dO, store, fwd=None, dbias=None, accumulate=False):
+    """ops.attn_fused_fwd / attn_fused_bwd without dropout, the backward over a hostile workspace.  `fwd`: a forward of the same
+    inputs and mode to reuse (it does not depend on dO)"""
+    B, T, _ = qkv.shape
+    if fwd is None:
+        fwd = ops.attn_fused_fwd(qkv, gate, tab, kpm, H, ATTN_SCALE, 0.0, 0, store_p=store)
+    O, lse, ps = fwd
+    fa_hostile_workspace(qkv.device, B, H, T)
+    dqkv, dgate, dtab = ops.attn_fused_bwd(qkv, O, dO, lse, gate, tab, kpm, H, ATTN_SCALE, 0.0, 0, dbias=dbias,
+                                           dbias_accumulate=accumulate, pstore=ps)
+    return {"O": O, "dqkv": dqkv, "dgate": dgate, "dtab": dtab, "dbias": dbias}, fwd
+
+
+def fa_autograd(qkv, gate, tab, kpm, H, dO, fused, store, p_drop=0.0, seed=0):
+    """F.AttnCoreFn forward and backward under the given switches (the caller restores them), over a hostile workspace"""
+    F.USE_FUSED_ATTENTION, F.ATTN_STORE_P = fused, store
+    qd = qkv.clone().requires_grad_(True)
+    gd = gate.clone().requires_grad_(True) if tab is not None else None
+    td = tab.clone().requires_grad_(True) if tab is not None else None
+    Od = F.AttnCoreFn.apply(qd, gd, td, kpm, H, ATTN_SCALE, p_drop, seed)
+    fa_hostile_workspace(qkv.device, qkv.shape[0], H, qkv.shape[1])
+    Od.backward(dO)
+    return {"O": Od.detach(), "dqkv": qd.grad, "dgate": gd.grad if tab is not None else None, "dtab": td.grad if tab is not None else None}
+
+
+def errd_to(a, b, scale):
+    """max |a - b| against a scale taken elsewhere (a slice whose own reference is zero)"""
+    v = ((a.detach().double() - b.detach().double()).abs().max() / scale).item()
+    return v if math.isfinite(v) else float("inf")
+
+
+def fa_mode_name(fused, store):
+    return ("fused, stored bits" if store == "bits" else "fused, stored P" if store else "fused, recompute") if fused else "unfused"
+
+
+@leaves_no_footprint
+def check_attention_reduce():
+    """Every path of fa_dtab_reduce_kernel and of the q|k|v bias gradient (fa_wave_colsum partial rows of the dQ and both dK/dV
+    kernels, wl_colsum_finish) at batch geometry, bf16, head_dim 64, against the float64 reference on the device.  The reduction
+    adds ntot = B * 4 * ceil(T / 128) partial rows: row slice s of 64 takes rows s + 64 u + 256 k, so the shapes are chosen for
+    ntot -- 68 (first use of u = 1), 264 twice (second sweep with a ragged end; once with 8 rows per item, once with 24, so that
+    item and row-in-item change in the middle of a sweep) and 768 (the training step's count).  One partial row in 768 moves dtab
+    by far less than the bound, so next to whole-batch parity each boundary row is probed ALONE: dO is zero outside the 32 query
+    rows of partial row r, dtab and the dq part of dbias then come from that row only and are compared with a B = 1 reference of
+    its item -- a reduction that drops or repeats the row is wrong by order 1.  Every backward runs over a workspace of 0xFF bytes
+    (the reduction reads ranges the dQ kernel never wrote and must select, never multiply)."""
+    out = []
+    saved = (F.USE_FUSED_ATTENTION, F.ATTN_STORE_P)
+    nan = float("nan")
+    forms = {False: ((torch.float32, False), (torch.bfloat16, True)), True: ((torch.bfloat16, False), (torch.float32, True))}
+    try:
+        for (B, H, T) in ATTN_REDUCE_SHAPES:
+            D = 64 * H
+            nrow, ntot = fa_partial_rows(B, T)
+            qkv, gate, tab, dO = fa_inputs(B, H, T)
+            ref = fa_ref64(qkv, gate, tab, None, H, dO)
+            fwds = {}
+            for store in (False, True):
+                for (bdt, acc) in forms[store]:
+                    tag = f"attention_reduce B={B} H={H} T={T} ntot={ntot} [{fa_mode_name(True, store)}]"
+                    if acc:   # (+)= onto a base of the gradient's own size
+                        dbias = (dgen(3 * D, seed=31) * (0.5 * ref["dbias"].abs().max().item())).to(bdt)
+                        want = dbias.double() + ref["dbias"]
+                    else:     # = into NaN-filled memory
+                        dbias = torch.full((3 * D,), nan, dtype=bdt, device=DEV)
+                        want = ref["dbias"]
+                    got, fwds[store] = fa_device(qkv, gate, tab, None, H, dO, store, fwd=fwds.get(store), dbias=dbias, accumulate=acc)
+                    if store:
+                        out.append((tag + " the forward returns a store", 0.0 if fwds[store][2] is not None else 1.0, 0.0))
+                    out.append((tag + " O", errd(got["O"], ref["O"]), TOLBF))
+                    for nm in ("dqkv", "dgate", "dtab"):
+                        out.append((tag + " " + nm, errd(got[nm], ref[nm]), 2 * TOLBF))
+                    out.append((tag + f" dbias[{str(bdt)[6:]}, accumulate={acc}]", errd(got["dbias"], want), 2 * TOLBF))
+            for r in sorted({r for r in ATTN_REDUCE_PROBES + (ntot - 1,) if r < ntot}):
+                bs, c = divmod(r, nrow)
+                lo, hi = 32 * c, min(32 * c + 32, T)   # (empty past T: everything must come out exactly zero then)
+                dOp = torch.zeros_like(dO)
+                dOp[bs, lo:hi] = dO[bs, lo:hi]
+                ref1 = fa_ref64(qkv[bs:bs + 1], gate[bs:bs + 1], tab, None, H, dOp[bs:bs + 1])
+                others = torch.ones(B, dtype=torch.bool, device=DEV)
+                others[bs] = False
+                for store in (False, True):
+                    rows = f"rows {lo}..{hi - 1}" if lo < hi else "no row below T"
+                    tag = f"attention_reduce B={B} H={H} T={T} partial row {r} of {ntot} alone (item {bs}, {rows}) [{fa_mode_name(True, store)}]"
+                    dbias = torch.full((3 * D,), nan, dtype=torch.float32, device=DEV)
+                    got, _ = fa_device(qkv, gate, tab, None, H, dOp, store, fwd=fwds[store], dbias=dbias)
+                    out.append((tag + " dtab", errd(got["dtab"], ref1["dtab"]), 2 * TOLBF))
+                    out.append((tag + " dbias", errd(got["dbias"], ref1["dbias"]), 2 * TOLBF))
+                    out.append((tag + " dqkv of the item", errd(got["dqkv"][bs], ref1["dqkv"][0]), 2 * TOLBF))
+                    out.append((tag + " dgate of the item", errd(got["dgate"][bs], ref1["dgate"][0]), 2 * TOLBF))
+                    out.append((tag + " dqkv, dgate of the other items == 0 (non-zero elements)",
+                                float(((got["dqkv"][others] != 0).sum() + (got["dgate"][others] != 0).sum()).item()), 0.0))
+        # TAB = false instantiation of the three backward kernels at batch geometry
+        B, H, T = 33, 2, 130
+        qkv, _, _, dO = fa_inputs(B, H, T, tabbed=False)
+        ref = fa_ref64(qkv, None, None, None, H, dO)
+        for store in (False, True):
+            tag = f"attention_reduce no bias B={B} H={H} T={T} [{fa_mode_name(True, store)}]"
+            dbias = torch.full((3 * 64 * H,), nan, dtype=torch.float32, device=DEV)
+            got, _ = fa_device(qkv, None, None, None, H, dO, store, dbias=dbias)
+            out.append((tag + " O", errd(got["O"], ref["O"]), TOLBF))
+            out.append((tag + " dqkv", errd(got["dqkv"], ref["dqkv"]), 2 * TOLBF))
+            out.append((tag + " dbias", errd(got["dbias"], ref["dbias"]), 2 * TOLBF))
+    finally:
+        F.USE_FUSED_ATTENTION, F.ATTN_STORE_P = saved
+    return out
+
+
+def attn_ragged_mask(T=300):
+    """key padding of the ragged batch: items 0..5 right-padded to ATTN_RAGGED_LENGTHS; item 6 with keys [0, 70) and [128, 192)
+    masked (its first 64-key tile is dead -- the online softmax meets a tile with no live key before any live one -- and a whole
+    dead tile lies between live ones); item 7 with one live key"""
+    kpm = torch.zeros(len(ATTN_RAGGED_LENGTHS) + 2, T, dtype=torch.uint8)
+    for b, n in enumerate(ATTN_RAGGED_LENGTHS):
+        kpm[b, n:] = 1
+    kpm[6, :70] = 1
+    kpm[6, 128:192] = 1
+    kpm[7, 1:] = 1
+    return kpm
+
+
+def fa_item_lines(out, tag, got, ref, D, single=(7,)):
+    """O, dqkv, dgate of every item against that item's own reference maximum (err()'s whole-tensor scale is set by the shortest
+    item: its dqkv maximum is some 20 times the full-length item's).  Items with ONE live key (`single`): every probability is
+    exactly 1, so the reference's dS -- and with it dq, dk and dgate -- is exactly zero and a ratio to the slice means nothing:
+    O and dv against the slice, dq | dk and dgate against the whole tensor's scale"""
+    B = ref["O"].shape[0]
+    qmax, gmax = ref["dqkv"].abs().max(), ref["dgate"].abs().max()
+    for b in range(B):
+        out.append((tag + f" item {b} O", errd(got["O"][b], ref["O"][b]), TOLBF))
+        if b in single:
+            out.append((tag + f" item {b} dv", errd(got["dqkv"][b, :, 2 * D:], ref["dqkv"][b, :, 2 * D:]), 2 * TOLBF))
+            out.append((tag + f" item {b} dq | dk (tensor scale)", errd_to(got["dqkv"][b, :, :2 * D], ref["dqkv"][b, :, :2 * D], qmax), 2 * TOLBF))
+            out.append((tag + f" item {b} dgate (tensor scale)", errd_to(got["dgate"][b], ref["dgate"][b], gmax), 2 * TOLBF))
+        else:
+            out.append((tag + f" item {b} dqkv", errd(got["dqkv"][b], ref["dqkv"][b]), 2 * TOLBF))
+            out.append((tag + f" item {b} dgate", errd(got["dgate"][b], ref["dgate"][b]), 2 * TOLBF))
+    out.append((tag + " dtab", errd(got["dtab"], ref["dtab"]), 2 * TOLBF))
+    masked = ref["kpm"].bool()
+    out.append((tag + " dk, dv of masked keys == 0 (non-zero elements)", float((got["dqkv"][..., D:][masked] != 0).sum().item()), 0.0))
+
+
+def fa_mask_lines(out, tag, masks, plain, live):
+    """forward, dQ and dK/dV keep masks of one mode (_attn_kernel_masks) against each other and against the plain forward's.  The
+    dQ read-out takes the sign of dS = P sc (keep - kappa) with kappa the row's kept mass: a row that keeps EVERY live key has
+    kappa = 1 and dS = 0 up to rounding, and says nothing (one row in 10^8 at 65 live keys, 9 in 16 at two, all at one); such rows
+    are left out of the dQ comparison -- a dQ kernel that drops other elements there misses the numerics that follow"""
+    kf, kq, kkv = masks
+    readable = (kf.sum(-1) < live.sum(-1)[:, None, None])[..., None]
+    if plain is not None:
+        out.append((tag + " storing fwd == plain fwd (mismatching elements)", float((kf != plain).sum().item()), 0.0))
+    out.append((tag + " mask fwd == dQ (mismatching elements)", float(((kf != kq) & readable).sum().item()), 0.0))
+    out.append((tag + " mask fwd == dK/dV (mismatching elements)", float((kf != kkv).sum().item()), 0.0))
+
+
+@leaves_no_footprint
+def check_attention_ragged():
+    """Key-padding masks the kernels accept and no other check sends (attn_ragged_mask), B = 8, H = 2, T = 300, bf16, head_dim 64,
+    against the float64 reference on the device, PER ITEM (fa_item_lines): without dropout in the recompute, stored-probability
+    and unfused forms, with dropout 0.25 in the three fused modes under the kernels' own mask, which must be the same in the
+    forward, dQ and dK/dV kernels.  dk and dv of masked keys are exactly zero, and every item computed alone (B = 1) gives the bits
+    it gives inside the batch.  The float64 reference of this batch (check_attention's draws, seeds 11..14) has slice maxima of
+    0.6 .. 2.7 (O) and 1.0 .. 23.9 (dqkv); rounding P to bf16 alone costs 1e-3 .. 2.3e-3 of a slice, a tenth of TOLBF, so the
+    project's bounds hold per item as they are."""
+    out = []
+    saved = (F.USE_FUSED_ATTENTION, F.ATTN_STORE_P)
+    try:
+        H, T = 2, 300
+        D = 64 * H
+        kpm = attn_ragged_mask(T).to(DEV)
+        B = kpm.shape[0]
+        qkv, gate, tab, dO = fa_inputs(B, H, T, host=True)
+        ref = fa_ref64(qkv, gate, tab, kpm, H, dO)
+        ref["kpm"] = kpm
+        batch = {}
+        for fused, store in ((True, False), (True, True), (False, False)):
+            got = batch[store if fused else "unfused"] = fa_autograd(qkv, gate, tab, kpm, H, dO, fused, store)
+            fa_item_lines(out, f"attention_ragged [{fa_mode_name(fused, store)}]", got, ref, D)
+        for store in (False, True):
+            for b in range(B):
+                one = fa_autograd(qkv[b:b + 1].contiguous(), gate[b:b + 1].contiguous(), tab, kpm[b:b + 1].contiguous(), H,
+                                  dO[b:b + 1].contiguous(), True, store)
+                diff = sum(same_bits(one[nm][0], batch[store][nm][b]) for nm in ("O", "dqkv", "dgate"))
+                out.append((f"attention_ragged [{fa_mode_name(True, store)}] item {b} alone == in the batch (O, dqkv, dgate that differ)", diff, 0.0))
+        seed, sc = 0x9E3779B97F4A7C15, 1.0 / (1.0 - ATTN_DROP)
+        live = ~kpm.bool().cpu()
+        plain = None
+        for store in (False, True, "bits"):
+            tag = f"attention_ragged dropout [{fa_mode_name(True, store)}]"
+            masks = _attn_kernel_masks(B, H, T, ATTN_DROP, seed, gate, tab, kpm, store_p=store)
+            fa_mask_lines(out, tag, masks, plain, live)
+            if plain is None:
+                plain = masks[0]
+                out.append((tag + " keep fraction of the live keys", abs(plain.float().sum().item() / (H * T * live.sum().item()) - (1 - ATTN_DROP)), 0.01))
+                refd = fa_ref64(qkv, gate, tab, kpm, H, dO, keep=plain.to(DEV), sc=sc)
+                refd["kpm"] = kpm
+            fa_item_lines(out, tag, fa_autograd(qkv, gate, tab, kpm, H, dO, True, store, ATTN_DROP, seed), refd, D)
+    finally:
+        F.USE_FUSED_ATTENTION, F.ATTN_STORE_P = saved
+    return out
+
+
+@leaves_no_footprint
+def check_attention_long():
+    """The fused kernels at and past FA_PSTORE_MAX_T = 1024 (bf16, head_dim 64, gate and table, float64 reference on the device):
+    T = 1024 -- the last length with a probability store, where the stored-P dK/dV kernel's per-row LDS arrays (FA_DKVP_ROWS) are
+    full --, 1025 (no store: ops.attn_fused_fwd returns None and AttnCoreFn under ATTN_STORE_P=True recomputes), 1153 with a
+    padded item, 1537 (30 s of audio is 1499 frames).  At T = 1025 the dropout modes that have no cap -- recompute and stored
+    bits -- must apply one mask in all three kernels, agree bit for bit, and match the reference under that mask."""
+    out = []
+    saved = (F.USE_FUSED_ATTENTION, F.ATTN_STORE_P)
+    try:
+        for (B, H, T, n1) in ATTN_LONG_CASES:
+            kpm = None
+            if n1 is not None:
+                kpm = torch.zeros(B, T, dtype=torch.uint8, device=DEV)
+                kpm[1, n1:] = 1
+            qkv, gate, tab, dO = fa_inputs(B, H, T)
+            ref = fa_ref64(qkv, gate, tab, kpm, H, dO)
+            stored = ops.attn_fused_fwd(qkv, gate, tab, kpm, H, ATTN_SCALE, 0.0, 0, store_p=True)[2] is not None
+            out.append((f"attention_long B={B} H={H} T={T} probability store " + ("returned" if T <= FA_PSTORE_MAX_T else "refused (None)"),
+                        0.0 if stored == (T <= FA_PSTORE_MAX_T) else 1.0, 0.0))
+            for store in (False, True):
+                tag = f"attention_long B={B} H={H} T={T} [{fa_mode_name(True, store)}{'' if stored or not store else ' -> recompute'}]"
+                got = fa_autograd(qkv, gate, tab, kpm, H, dO, True, store)
+                out.append((tag + " O", errd(got["O"], ref["O"]), TOLBF))
+                for nm in ("dqkv", "dgate", "dtab"):
+                    out.append((tag + " " + nm, errd(got[nm], ref[nm]), 2 * TOLBF))
+        B, H, T = 1, 1, 1025
+        seed, sc = 77, 1.0 / (1.0 - ATTN_DROP)
+        qkv, gate, tab, dO = fa_inputs(B, H, T)
+        live = torch.ones(B, T, dtype=torch.bool)
+        plain, res = None, {}
+        for store in (False, "bits"):
+            tag = f"attention_long dropout B={B} H={H} T={T} [{fa_mode_name(True, store)}]"
+            masks = _attn_kernel_masks(B, H, T, ATTN_DROP, seed, gate, tab, None, store_p=store)
+            fa_mask_lines(out, tag, masks, plain, live)
+            if plain is None:
+                plain = masks[0]
+                out.append((tag + " keep fraction", abs(plain.float().mean().item() - (1 - ATTN_DROP)), 0.01))
+                refd = fa_ref64(qkv, gate, tab, None, H, dO, keep=plain.to(DEV), sc=sc)
+            got = res[store] = fa_autograd(qkv, gate, tab, None, H, dO, True, store, ATTN_DROP, seed)
+            out.append((tag + " O vs fp64 with the kernel's mask", errd(got["O"], refd["O"]), TOLBF))
+            for nm in ("dqkv", "dgate", "dtab"):
+                out.append((tag + " " + nm + " vs fp64 with the kernel's mask", errd(got[nm], refd[nm]), 2 * TOLBF))
+        for nm in ("O", "dqkv", "dgate"):
+            out.append((f"attention_long dropout B={B} H={H} T={T} stored bits == recompute: {nm} (bits differ)",
+                        same_bits(res[False][nm], res["bits"][nm]), 0.0))
+    finally:
+        F.USE_FUSED_ATTENTION, F.ATTN_STORE_P = saved
+    return out
+
+
 GROUPS = {
     "gemm": check_gemm, "gemm_pp": check_gemm_pp, "gemm_pp3": check_gemm_pp3, "gemm_w4": check_gemm_w4, "gemm_grouped": check_gemm_grouped, "gemm_race": check_gemm_race, "layernorm": check_layernorm, "rowops": check_rowops, "conv0": check_conv0, "conv0_ln": check_conv0_ln, "conv_ln_block": check_conv_ln_block,
     "conv_ln_block_wide": check_conv_ln_block_wide, "convstack": check_convstack, "convstack_wide": check_convstack_wide, "attention": check_attention, "posconv": check_posconv, "gemm_colsum": check_gemm_colsum,
@@ -3203,7 +3531,13 @@ GROUPS = {
     "layernorm_rows": check_layernorm_rows, "layernorm_dropout_ref": check_layernorm_dropout_ref, "colsum_rows": check_colsum_rows,
     "flat_strided": check_flat_strided, "masked_pred_head": check_masked_pred_head, "loss_rows_capped": check_loss_rows_capped,
     "posconv_batch": check_posconv_batch, "posconv_frames": check_posconv_frames, "posconv_layouts": check_posconv_layouts,
+    "attention_reduce": check_attention_reduce, "attention_ragged": check_attention_ragged, "attention_long": check_attention_long,
 }
+# gemm_race's split-K case grows ops' "main" workspace to 63 MiB (7 fp32 slabs of 3072 x 768) while the tensors of the cases before
+# lie freed in the cache: when the groups run in a process of their own (pytest tests/test_kernels_gpu.py), the workspace is cut
+# out of the middle of a cached 192 MiB block and pins 54 + 75 MiB of stale memory, and layernorm_rows' poisoned 16 MiB request
+# is handed the 54 MiB fragment instead of the NaN-filled block (measured on the MI355X, with and without the attention groups)
+GROUPS["gemm_race"] = leaves_no_footprint(check_gemm_race)
 
 if __name__ == "__main__":
     import json
